@@ -10,9 +10,13 @@ N = 1: configs[1] (bs = 16 pairs on one MI355X).  N > 1: the same 16 pairs PER G
 either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, for a plain
 `python bench.py --gpus N`, started by this file itself as N fresh child processes BEFORE the parent touches the GPU -
 and one bucketed RCCL all-reduce of the flat trainable-gradient buffer per step, issued from inside the last backward.
-Prints ONE JSON line on rank 0 with `roofline` (dominant hand-written kernel: the fused causal SDPA backward, timed live
-with HIP events on the launch stream) and `cpu_baseline` (the oracle's CPU restatement timed on the host cores, rank 0,
-N = 1 only, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run only sets up, warms up, times the --steps steps and reports them (`roofline` and
+`cpu_baseline` are null).  --full adds the measurements that take work of their own: `roofline` (dominant hand-written kernel:
+the fused causal SDPA backward, timed live with HIP events on the launch stream inside the timed steps, plus a microbenchmark
+after them) and `cpu_baseline` (the oracle's CPU restatement timed on the host cores, rank 0, N = 1 only, bounded sample);
+--no-roofline / --no-cpu-baseline drop either of them again.
+--dump-outputs DIR (rank 0) writes what the last timed step computed as float32 / float64 .npy files: the loss and its two
+terms, and a fixed, seeded sample of the fp32 trainable gradient and of the fp32 master weights after the AdamW update.
 """
 import argparse
 import json
@@ -321,7 +325,14 @@ def physical_cores():
     except Exception:
         pass
     n = max(1, len(cpus) // smt)
-    return n, "%d logical CPUs in the affinity mask / SMT width %d" % (len(cpus), smt)
+    how = "%d logical CPUs in the affinity mask / SMT width %d" % (len(cpus), smt)
+    try:      # a CPU quota narrower than the affinity mask (shared hosts) is announced through OMP_NUM_THREADS: stay inside it
+        cap = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        cap = 0
+    if 0 < cap < n:
+        n, how = cap, how + ", capped by OMP_NUM_THREADS=%d" % cap
+    return n, how
 
 
 def _median_time(fn, reps=3):
@@ -416,6 +427,30 @@ def cpu_baseline():
                       "layers + 4 heads (CLIP tower omitted, <1%%); value = the faster dtype (%s)" % (cores, how, desc, best)}
 
 
+DUMP_SAMPLE = 4 * 2 ** 20      # flat indices drawn for the sampled vectors of --dump-outputs (2 x 16 MiB of float32 at most)
+
+
+def dump_outputs(path, loss, parts, flat, seed=0):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it - the loss and its two terms (float64)
+    and, after the AdamW update, the fp32 gradient accumulator and the fp32 master weights of the trainables at a fixed, seeded
+    sample of flat indices (float32; every index when there are no more than DUMP_SAMPLE).  The sample depends on the parameter
+    count only, so two builds of the same geometry are compared entry for entry."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if flat.total <= DUMP_SAMPLE:
+        idx = np.arange(flat.total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.total, DUMP_SAMPLE, dtype=np.int64))
+    sel = torch.from_numpy(idx).to(flat.grad.device)
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64),
+              "alignment": np.array([float(parts["alignment"])], dtype=np.float64),
+              "divergence": np.array([float(parts["divergence"])], dtype=np.float64),
+              "grad_sample": flat.grad.index_select(0, sel).float().cpu().numpy(),
+              "master_sample": flat.master.index_select(0, sel).float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes of this file (one per GPU) and wait for them.
     Runs before this process has made any GPU call (torch.cuda.device_count() does not initialise the runtime); nothing is
@@ -475,9 +510,19 @@ def main():
     ap.add_argument("--resp-len", type=int, default=0,
                     help="response length in tokens (default: fill T to 2048 / 4096 as BASELINE.md section 3 prescribes; other values "
                          "mark the line invalid - e.g. 128 resembles the real HALVA data, where the shared prefix dominates)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure `roofline` (SDPA launches of the timed steps + a kernel microbenchmark) and `cpu_baseline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    roofline_on = args.full and not args.no_roofline
+    cpu_baseline_on = args.full and not args.no_cpu_baseline
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -675,8 +720,8 @@ def main():
             print("%-14s %8.2f ms %5d calls  shapes %s\n      %s" % (e.key, e.self_device_time_total / 1e3, e.count, str(e.input_shapes)[:110],
                                                                    " <- ".join(str(f).split("/")[-1] for f in e.stack[:5])), file=sys.stderr)
     from halva_amd import kernels as HK
-    HK.sdpa_bwd_probe = [] if not args.no_roofline else None      # HIP events around every SDPA-backward launch of the timed steps
-    HK.sdpa_fwd_probe = [] if not args.no_roofline else None      # ... and every forward launch
+    HK.sdpa_bwd_probe = [] if roofline_on else None      # HIP events around every SDPA-backward launch of the timed steps
+    HK.sdpa_fwd_probe = [] if roofline_on else None      # ... and every forward launch
     del comm_probe[:]
     trace = ClockTrace(dev, os.environ["HALVA_BENCH_CLOCK_TRACE"]) if (os.environ.get("HALVA_BENCH_CLOCK_TRACE") and ctx.rank == 0) else None
     dp.barrier(ctx)
@@ -695,16 +740,18 @@ def main():
     dt = dp.max_scalar(dt, ctx)
     loss_val = float(last)
     pairs_per_s = ctx.world * B * args.steps / dt
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, last, eng.last_parts, flat)
 
-    if not args.no_roofline:
+    if roofline_on:
         torch.cuda.empty_cache()      # hand the step's cached blocks back before the kernel microbenchmark allocates its own
-    roof = None if args.no_roofline else sdpa_roofline(dev)
+    roof = sdpa_roofline(dev) if roofline_on else None
     if roof is not None and probe:
         roof = in_step_roofline(probe, eng.last_layout, roof)
         if fprobe:      # (roofline.fwd stays the micro-benchmark at the plain per-layer shape; this is the step's own mix of launches)
             roof["fwd_in_step"] = in_step_forward(fprobe, eng.last_layout)
     cpu = None
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if ctx.rank == 0 and ctx.world == 1 and cpu_baseline_on:
         cpu = cpu_baseline()
     comm = None
     if reducer is not None and comm_probe:

@@ -4,7 +4,7 @@
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
 HALVA_OVERLAP_REF=1 timeout 900 python3 -m pytest tests/test_dpa_step_gpu.py -x -q -m gpu > $O/r05_overlap_pytest.log 2>&1; tail -3 $O/r05_overlap_pytest.log
 for v in 0 1 0 1; do
-  HALVA_OVERLAP_REF=$v python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_overlap$v.json 2> $O/r05_ab_overlap$v.err || tail -5 $O/r05_ab_overlap$v.err
+  HALVA_OVERLAP_REF=$v python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_overlap$v.json 2> $O/r05_ab_overlap$v.err || tail -5 $O/r05_ab_overlap$v.err
   python3 - $O/r05_ab_overlap$v.json "overlap_ref=$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

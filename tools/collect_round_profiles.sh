@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/ holds for one round, from the CURRENT build (run on the GPU box: HALVA_COMMIT=<sha> gpurun -- bash tools/collect_round_profiles.sh r03):
-#   <tag>_bench_line.json / _bench_stdout.log        the default `python bench.py` line, with the in-kernel clock trace (HALVA_BENCH_CLOCK_TRACE)
+#   <tag>_bench_line.json / _bench_stdout.log        the `python bench.py --full` line, with the in-kernel clock trace (HALVA_BENCH_CLOCK_TRACE)
 #   <tag>_clock_trace_bench.json                       its samples
 #   <tag>_step_kernel_stats.csv / _step_summary.md     ONE steady-state step: (rocprofv3 --stats of --steps 3) - (--steps 1), per kernel (tools/steady_state_stats.py)
 #   <tag>_sdpa_pmc.json                                FETCH_SIZE / WRITE_SIZE of the SDPA kernels (microbench shape + in the step), tools/make_pmc_json.py
@@ -28,7 +28,7 @@ bash tools/pmc_rowops.sh $tag > $OUT/rowops.log 2>&1; cp gpurun_out/${tag}_rowop
 python3 tools/clock_under_load.py $OUT/${tag}_clock_under_load.json > $OUT/clock_under_load.log 2>&1
 # the bench line last: it quotes the traffic record collected above when that has been copied to profiles/ (the copy below makes it so on the box)
 cp $OUT/${tag}_sdpa_pmc.json profiles/${tag}_sdpa_pmc.json
-HALVA_BENCH_CLOCK_TRACE=$OUT/${tag}_clock_trace_bench.json python3 bench.py > $OUT/${tag}_bench_stdout.log 2>&1
+HALVA_BENCH_CLOCK_TRACE=$OUT/${tag}_clock_trace_bench.json python3 bench.py --full > $OUT/${tag}_bench_stdout.log 2>&1
 grep '^{' $OUT/${tag}_bench_stdout.log | tail -1 > $OUT/${tag}_bench_line.json
 rm -rf $OUT/stats1 $OUT/stats3 $OUT/traffic $OUT/traffic_step gpurun_out/pmc_sdpa_$tag gpurun_out/pmc_rowops_$tag
 ls -la $OUT; cat $OUT/${tag}_step_summary.md; tail -c 1200 $OUT/${tag}_bench_stdout.log

@@ -23,7 +23,7 @@ unset HALVA_SDPA_DQ3
 cd $R
 for cfg in "1 1" "0 1" "1 0" "1 1" "0 1" "1 0"; do
   set -- $cfg
-  HALVA_ROPE_FUSED_BWD=$1 HALVA_SDPA_DQ3=$2 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rope$1_dq3$2.json 2>/dev/null
+  HALVA_ROPE_FUSED_BWD=$1 HALVA_SDPA_DQ3=$2 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rope$1_dq3$2.json 2>/dev/null
   python3 - $O/r05_ab_rope$1_dq3$2.json "rope_fused=$1 dq3=$2" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -7,7 +7,7 @@ timeout 900 python3 -m pytest tests/test_dpa_step_gpu.py tests/test_vila_gpu.py 
 timeout 1500 python3 -m pytest tests/test_fullwidth_layer_parity_gpu.py -x -q -m gpu -s --durations=8 > $O/r05_fullwidth_parity.log 2>&1; tail -16 $O/r05_fullwidth_parity.log
 for cfg in "1 1" "0 1" "1 0" "1 1" "0 1"; do
   set -- $cfg
-  HALVA_ROPE_FUSED_BWD=$1 HALVA_FWD3_REPAIR=$2 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rope$1_repair$2.json 2>/dev/null
+  HALVA_ROPE_FUSED_BWD=$1 HALVA_FWD3_REPAIR=$2 python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rope$1_repair$2.json 2>/dev/null
   python3 - $O/r05_ab_rope$1_repair$2.json "rope_fused=$1 repair=$2" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -4,7 +4,7 @@
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
 for v in old new old new; do
   if [ $v = old ]; then export HALVA_HIP_LIB=$R/halva_amd/libhalva_hip_rowold.so; else unset HALVA_HIP_LIB; fi
-  python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rows_$v.json 2>/dev/null
+  python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $O/r05_ab_rows_$v.json 2>/dev/null
   python3 - $O/r05_ab_rows_$v.json "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
