@@ -1,0 +1,272 @@
+// Single-token decode over a KV cache (greedy generation, halva_amd/decode.py) on gfx950: RoPE + cache append of the new token, and
+// split-KV ("flash-decoding") attention of one query row per (sequence, head).  Both are HBM-bound and use no MFMA: M = 1 per head.
+//
+// Cache layout, per layer: K, V bf16 [B, H, Lcap, 128]; lens int32 [B] on the device (never a launch-time host value, so the step can
+// be captured in a graph later).  Slots at or beyond lens[b] are never read.
+#include "common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int kDecD = 128;          // head_dim of the LLaVA-1.5 decoder
+constexpr int kDecChunks = kDecD / 8;      // 16-byte pieces per head row
+constexpr int kDecWaves = 4;        // waves per split-KV workgroup
+
+__device__ __forceinline__ void dec_unpack8(const u32x4& v, float (&f)[8]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = bf16_lo(v[i]);
+        f[2 * i + 1] = bf16_hi(v[i]);
+    }
+}
+__device__ __forceinline__ u32x4 dec_pack8(const float (&f)[8]) {
+    u32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// RoPE of the new token + cache append.  One workgroup per sequence b: every thread reads lens[b] before the barrier, thread 0 advances
+// it after, so no other reader of this launch sees the new value.  qkv row b = [3, H, D]; q rotated in place (rope_qk_kernel's arithmetic),
+// rotated k and plain v written to slot lens[b].
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void decode_rope_append_kernel(u32x4* __restrict__ qkv, int64_t ldq_chunks, const u32x4* __restrict__ cosb,
+                                                                 const u32x4* __restrict__ sinb, int max_pos, u32x4* __restrict__ kc,
+                                                                 u32x4* __restrict__ vc, int32_t* __restrict__ lens, int H, int Lcap) {
+    constexpr int CH = kDecChunks / 2;          // 16-byte pieces per half head row
+    const int b = blockIdx.x;
+    const int p = lens[b];
+    const bool ok = p >= 0 && p < Lcap && p < max_pos;      // (the host sizes the cache; a full one is left untouched, never overrun)
+    u32x4* row = qkv + (int64_t)b * ldq_chunks;
+    if (ok) {
+        for (int i = threadIdx.x; i < 2 * H * CH; i += blockDim.x) {
+            const int c = i % CH;
+            const int h = (i / CH) % H;
+            const int part = i / (CH * H);      // 0 = q, 1 = k
+            const int64_t base = (int64_t)(part * H + h) * kDecChunks + c;
+            float x1[8], x2[8], cs[8], sn[8], y1[8], y2[8];
+            dec_unpack8(row[base], x1);
+            dec_unpack8(row[base + CH], x2);
+            dec_unpack8(cosb[(int64_t)p * CH + c], cs);
+            dec_unpack8(sinb[(int64_t)p * CH + c], sn);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rope_pair(x1[j], x2[j], cs[j], sn[j], y1[j], y2[j]);
+            if (part == 0) {
+                row[base] = dec_pack8(y1);
+                row[base + CH] = dec_pack8(y2);
+            } else {
+                u32x4* dst = kc + (((int64_t)b * H + h) * Lcap + p) * kDecChunks + c;
+                dst[0] = dec_pack8(y1);
+                dst[CH] = dec_pack8(y2);
+            }
+        }
+        for (int i = threadIdx.x; i < H * kDecChunks; i += blockDim.x) {
+            const int h = i / kDecChunks, c = i % kDecChunks;
+            vc[(((int64_t)b * H + h) * Lcap + p) * kDecChunks + c] = row[(int64_t)(2 * H + h) * kDecChunks + c];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && ok) lens[b] = p + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Split-KV attention, partial pass.  Workgroup (chunk c, head h, sequence b) covers keys [c KC, (c + 1) KC) ∩ [0, lens[b]); 4 waves of
+// KC / 4 keys each.  A wave takes 4 keys per step, 16 lanes per key row (one 16-byte piece of K and V per lane, straight to VGPRs - all
+// of the wave's K and V loads are issued before the first dot).  Scores in fp32 in the log2 domain (q pre-scaled by log2(e) / sqrt(D)).
+// The 4 waves combine in LDS in a fixed order; the chunk's (m, l, o[128]) go to the fp32 workspace.  Nothing here depends on B or on
+// the other rows: row b's result is bitwise the same in any batch.
+// ---------------------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void decode_attn_partial_kernel(const u32x4* __restrict__ q, int64_t ldq_chunks, const u32x4* __restrict__ kc,
+                                                                  const u32x4* __restrict__ vc, const int32_t* __restrict__ lens, int H, int Lcap,
+                                                                  int nchunk_cap, float qscale, float* __restrict__ ws_o,
+                                                                  float* __restrict__ ws_ml) {
+    constexpr int NI = KC / (4 * kDecWaves);       // steps of 4 keys per wave
+    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int len = min(lens[b], Lcap);
+    const int k0 = c * KC;
+    if (k0 >= len) return;                         // (uniform over the workgroup: no barrier is skipped by part of it)
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int sub = lane & 15, grp = lane >> 4;
+    const int64_t bh = (int64_t)b * H + h;
+    float qf[8];
+    dec_unpack8(q[(int64_t)b * ldq_chunks + h * kDecChunks + sub], qf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[j] *= qscale;
+    const u32x4* kb = kc + bh * Lcap * kDecChunks + sub;
+    const u32x4* vb = vc + bh * Lcap * kDecChunks + sub;
+    const int kw0 = k0 + w * (KC / kDecWaves) + grp;
+    u32x4 kr[NI], vr[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int key = kw0 + 4 * i;
+        kr[i] = key < len ? kb[(int64_t)key * kDecChunks] : u32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int key = kw0 + 4 * i;
+        vr[i] = key < len ? vb[(int64_t)key * kDecChunks] : u32x4{0, 0, 0, 0};
+    }
+    float s[NI];
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        float f[8];
+        dec_unpack8(kr[i], f);
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d = fmaf(qf[j], f[j], d);
+        d += __shfl_xor(d, 8, 64);
+        d += __shfl_xor(d, 4, 64);
+        d += __shfl_xor(d, 2, 64);
+        d += __shfl_xor(d, 1, 64);
+        s[i] = (kw0 + 4 * i < len) ? d : -INFINITY;
+        m = fmaxf(m, s[i]);
+    }
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (m != -INFINITY) {                          // (a wave whose keys all lie beyond lens[b] contributes nothing)
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const float p = exp2f(s[i] - m);
+            float f[8];
+            dec_unpack8(vr[i], f);
+            l += p;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = fmaf(p, f[j], o[j]);
+        }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        o[j] += __shfl_xor(o[j], 16, 64);
+        o[j] += __shfl_xor(o[j], 32, 64);
+    }
+    __shared__ float s_o[kDecWaves][kDecD];
+    __shared__ float s_ml[kDecWaves][2];
+    if (lane < 16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s_o[w][sub * 8 + j] = o[j];
+    }
+    if (lane == 0) {
+        s_ml[w][0] = m;
+        s_ml[w][1] = l;
+    }
+    __syncthreads();
+    if (threadIdx.x < kDecD) {
+        const int d = threadIdx.x;
+        float M = s_ml[0][0];                      // finite: key k0 < len belongs to wave 0
+#pragma unroll
+        for (int ww = 1; ww < kDecWaves; ++ww) M = fmaxf(M, s_ml[ww][0]);
+        float acc = 0.f, L = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < kDecWaves; ++ww) {
+            const float f = s_ml[ww][0] == -INFINITY ? 0.f : exp2f(s_ml[ww][0] - M);
+            acc = fmaf(f, s_o[ww][d], acc);
+            L = fmaf(f, s_ml[ww][1], L);
+        }
+        const int64_t slot = bh * nchunk_cap + c;
+        ws_o[slot * kDecD + d] = acc;
+        if (d == 0) {
+            ws_ml[slot * 2] = M;
+            ws_ml[slot * 2 + 1] = L;
+        }
+    }
+}
+
+// Combine pass: one workgroup of 128 threads per (head, sequence) reduces the ceil(lens[b] / KC) partials in chunk order.
+template <int KC>
+__global__ __launch_bounds__(128) void decode_attn_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
+                                                                  const int32_t* __restrict__ lens, int H, int Lcap, int nchunk_cap,
+                                                                  bf16_t* __restrict__ out, int64_t ld_out) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    const int len = min(lens[b], Lcap);
+    const int n = len > 0 ? (len + KC - 1) / KC : 0;
+    const int64_t slot0 = ((int64_t)b * H + h) * nchunk_cap;
+    float M = -INFINITY;
+    for (int c = 0; c < n; ++c) M = fmaxf(M, ws_ml[(slot0 + c) * 2]);
+    float acc = 0.f, L = 0.f;
+    for (int c = 0; c < n; ++c) {
+        const float f = exp2f(ws_ml[(slot0 + c) * 2] - M);
+        acc = fmaf(f, ws_o[(slot0 + c) * kDecD + d], acc);
+        L = fmaf(f, ws_ml[(slot0 + c) * 2 + 1], L);
+    }
+    out[(int64_t)b * ld_out + h * kDecD + d] = f32_to_bf16(n > 0 ? acc / L : 0.f);
+}
+
+constexpr int kDecodeKC = 256;      // keys per split-KV chunk (tools/bench_decode.py: 4.85 TB/s at 256, 4.73 at 128, 4.54 at 64)
+
+int64_t decode_ws_bytes(int B, int H, int Lcap, int kc) {
+    if (B <= 0 || H <= 0 || Lcap <= 0) return 0;
+    return (int64_t)B * H * ((Lcap + kc - 1) / kc) * (kDecD + 2) * (int64_t)sizeof(float);
+}
+
+template <int KC>
+void launch_decode_attn(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out, int64_t ld_out,
+                        float* ws, int B, int H, int Lcap, float scale, hipStream_t stream) {
+    const int nchunk_cap = (Lcap + KC - 1) / KC;
+    float* ws_o = ws;
+    float* ws_ml = ws + (int64_t)B * H * nchunk_cap * kDecD;
+    hipLaunchKernelGGL(decode_attn_partial_kernel<KC>, dim3(nchunk_cap, H, B), dim3(64 * kDecWaves), 0, stream, (const u32x4*)q, ldq / 8,
+                       (const u32x4*)kcache, (const u32x4*)vcache, lens, H, Lcap, nchunk_cap, scale * 1.4426950408889634f, ws_o, ws_ml);
+    hipLaunchKernelGGL(decode_attn_combine_kernel<KC>, dim3(H, B), dim3(kDecD), 0, stream, ws_o, ws_ml, lens, H, Lcap, nchunk_cap,
+                       (bf16_t*)out, ld_out);
+}
+
+}  // namespace
+
+extern "C" int halva_decode_attn_kc(void) { return kDecodeKC; }
+
+extern "C" int64_t halva_decode_attn_ws_bytes(int B, int H, int Lcap) { return decode_ws_bytes(B, H, Lcap, kDecodeKC); }
+
+extern "C" int halva_decode_rope_append(void* qkv, int64_t ldqkv, const void* cos, const void* sin, int max_pos, void* kcache, void* vcache,
+                                        int32_t* lens, int B, int H, int D, int Lcap, void* stream) {
+    HALVA_CHECK_ARG(qkv && cos && sin && kcache && vcache && lens, "decode_rope_append: null pointer");
+    HALVA_CHECK_ARG(D == kDecD, "decode_rope_append: head_dim=%d (only 128)", D);
+    HALVA_CHECK_ARG(B > 0 && H > 0 && Lcap > 0 && max_pos > 0, "decode_rope_append: bad B=%d / H=%d / Lcap=%d / max_pos=%d", B, H, Lcap, max_pos);
+    HALVA_CHECK_ARG(ldqkv >= 3LL * H * D && ldqkv % 8 == 0, "decode_rope_append: row stride %lld (needs >= 3*H*D and a multiple of 8)",
+                    (long long)ldqkv);
+    HALVA_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)cos | (uintptr_t)sin | (uintptr_t)kcache | (uintptr_t)vcache) % 16 == 0,
+                    "decode_rope_append: pointers must be 16-byte aligned");
+    hipLaunchKernelGGL(decode_rope_append_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (u32x4*)qkv, ldqkv / 8, (const u32x4*)cos,
+                       (const u32x4*)sin, max_pos, (u32x4*)kcache, (u32x4*)vcache, lens, H, Lcap);
+    HALVA_CHECK_LAUNCH("decode_rope_append");
+    return HALVA_OK;
+}
+
+static int decode_attn(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out, int64_t ld_out,
+                       void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, int kc, void* stream) {
+    HALVA_CHECK_ARG(q && kcache && vcache && lens && out && ws, "decode_attn: null pointer");
+    HALVA_CHECK_ARG(D == kDecD, "decode_attn: head_dim=%d (only 128)", D);
+    HALVA_CHECK_ARG(B > 0 && H > 0 && Lcap > 0 && H <= 65535 && B <= 65535, "decode_attn: bad B=%d / H=%d / Lcap=%d", B, H, Lcap);
+    HALVA_CHECK_ARG(kc == 64 || kc == 128 || kc == 256, "decode_attn: chunk of %d keys (64, 128 or 256)", kc);
+    HALVA_CHECK_ARG(ldq >= (int64_t)H * D && ldq % 8 == 0, "decode_attn: q row stride %lld (needs >= H*D and a multiple of 8)", (long long)ldq);
+    HALVA_CHECK_ARG(ld_out >= (int64_t)H * D, "decode_attn: out row stride %lld < H*D", (long long)ld_out);
+    HALVA_CHECK_ARG(((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)ws) % 16 == 0,
+                    "decode_attn: q / cache / workspace pointers must be 16-byte aligned");
+    const int64_t need = decode_ws_bytes(B, H, Lcap, kc);
+    HALVA_CHECK_ARG(ws_bytes >= need, "decode_attn: workspace of %lld bytes, %lld needed (halva_decode_attn_ws_bytes)", (long long)ws_bytes,
+                    (long long)need);
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)D);
+    switch (kc) {
+        case 64: launch_decode_attn<64>(q, ldq, kcache, vcache, lens, out, ld_out, (float*)ws, B, H, Lcap, scale, (hipStream_t)stream); break;
+        case 128: launch_decode_attn<128>(q, ldq, kcache, vcache, lens, out, ld_out, (float*)ws, B, H, Lcap, scale, (hipStream_t)stream); break;
+        default: launch_decode_attn<256>(q, ldq, kcache, vcache, lens, out, ld_out, (float*)ws, B, H, Lcap, scale, (hipStream_t)stream); break;
+    }
+    HALVA_CHECK_LAUNCH("decode_attn");
+    return HALVA_OK;
+}
+
+extern "C" int halva_decode_attn(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out,
+                                 int64_t ld_out, void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, void* stream) {
+    return decode_attn(q, ldq, kcache, vcache, lens, out, ld_out, ws, ws_bytes, B, H, D, Lcap, scale, kDecodeKC, stream);
+}
+
+extern "C" int halva_decode_attn_chunked(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out,
+                                         int64_t ld_out, void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, int kc,
+                                         void* stream) {
+    return decode_attn(q, ldq, kcache, vcache, lens, out, ld_out, ws, ws_bytes, B, H, D, Lcap, scale, kc, stream);
+}

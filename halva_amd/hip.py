@@ -59,6 +59,10 @@ SIGNATURES = {
     "halva_probe_layouts": [_P, _I, _P],
     "halva_clock_probe": [_P, _I, _I, _P],
     "halva_sdpa_block_pairs": [_I, _I, _I, _I, _P],
+    "halva_decode_rope_append": [_P, _L, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
+    "halva_decode_attn": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
+    "halva_decode_attn_kc": [],
+    "halva_decode_attn_chunked": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
 }
 
 
@@ -98,6 +102,8 @@ def load():
         fn.argtypes = args
     lib.halva_sdpa_bwd_ws_bytes.restype = c_int64
     lib.halva_sdpa_bwd_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.halva_decode_attn_ws_bytes.restype = c_int64
+    lib.halva_decode_attn_ws_bytes.argtypes = [c_int, c_int, c_int]
     _lib = lib
     return lib
 

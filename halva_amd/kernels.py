@@ -268,6 +268,49 @@ def sdpa_causal(qkv, seq_start, seq_len, H, D, br_a=None, br_b=None):
     return _SdpaCausal.apply(qkv, seq_start, seq_len, H, D, None, None, None, None if br_a is None else (br_a, br_b, None))
 
 
+# ------------------------------------------------------------------------------------------------
+# KV-cached decoding (halva_amd/decode.py): forward only, no autograd
+def decode_kc():
+    """Keys per split-KV chunk of halva_decode_attn (a library constant)."""
+    return int(hip.load().halva_decode_attn_kc())
+
+
+def decode_ws_bytes(B, H, Lcap, kc=None):
+    """Workspace bytes of decode_attention (kc: the chunk of the measurement entry, None = the library's constant)."""
+    if kc is None:
+        return int(hip.load().halva_decode_attn_ws_bytes(B, H, Lcap))
+    return B * H * ((Lcap + kc - 1) // kc) * (128 + 2) * 4
+
+
+def decode_rope_append(qkv, cos, sin, kcache, vcache, lens, H, D):
+    """qkv [B, 3*H*D] (new tokens): q rotated in place at position lens[b], rotated k / plain v written to slot lens[b] of the
+    [B, H, Lcap, D] caches, lens[b] += 1 (halva_decode_rope_append)."""
+    _chk(qkv, torch.bfloat16, "qkv"), _chk(kcache, torch.bfloat16, "kcache"), _chk(vcache, torch.bfloat16, "vcache")
+    _chk(lens, torch.int32, "lens")
+    B, Lcap = qkv.shape[0], kcache.shape[2]
+    call("halva_decode_rope_append", ptr(qkv), qkv.shape[-1], ptr(cos), ptr(sin), cos.shape[0], ptr(kcache), ptr(vcache), ptr(lens), B, H, D,
+         Lcap, stream_ptr())
+    return qkv
+
+
+def decode_attention(q, kcache, vcache, lens, ws, H, D, out_width=None, ldq=None, kc=None):
+    """softmax(q K^T / sqrt(D)) V over the first lens[b] cache slots for one query row per (b, h) -> bf16 [B, out_width] (left H*D
+    columns written).  q: [B, ldq] rows whose first H*D columns are the query (the rotated q third of the qkv rows).
+    kc: a chunk size other than the library's (halva_decode_attn_chunked; measurement only)."""
+    _chk(q, torch.bfloat16, "q"), _chk(kcache, torch.bfloat16, "kcache"), _chk(vcache, torch.bfloat16, "vcache")
+    _chk(lens, torch.int32, "lens")
+    B, Lcap = q.shape[0], kcache.shape[2]
+    width = out_width or H * D
+    out = torch.empty(B, width, dtype=torch.bfloat16, device=q.device)
+    args = (ptr(q), ldq or q.shape[-1], ptr(kcache), ptr(vcache), ptr(lens), ptr(out), width, ptr(ws), ws.numel() * ws.element_size(), B, H, D,
+            Lcap, 0.0)
+    if kc is None:
+        call("halva_decode_attn", *args, stream_ptr())
+    else:
+        call("halva_decode_attn_chunked", *args, int(kc), stream_ptr())
+    return out
+
+
 def sdpa_full(qkv, H, D, scale=0.0):
     """Non-causal attention of the frozen CLIP / SigLIP tower (forward only).  qkv [N, S, 3*H*D] -> [N, S, H*D].
     scale 0 = 1/sqrt(D); SigLIP's 72-wide heads run zero-padded to D=128 with scale = 72**-0.5."""

@@ -394,21 +394,40 @@ class DecoderLayer(nn.Module):
     def groups(self):
         return (("self_attn", self.qkv), ("self_attn", self.o), ("mlp", self.gate_up), ("mlp", self.down))
 
-    def forward(self, x, info, use_lora=True, own_x=False, rows=None):
+    def forward(self, x, info, use_lora=True, own_x=False, rows=None, kv_hook=None):
         """own_x: the caller will not look at `x` again (it is the previous layer's output): without autograd the residual adds then
         run in place on it.
         rows: int64 [n] distinct flat row indices into [S * T] (the TOP layer only, LlamaModel.run_layers): everything behind the
-        attention is row-wise, so the o projection, the post-attention norm and the MLP run on those rows alone and [n, d] is returned."""
+        attention is row-wise, so the o projection, the post-attention norm and the MLP run on those rows alone and [n, d] is returned.
+        kv_hook: callable(qkv) handed the rotated [S, T, 3*H*D] projection after the attention (the prompt pass of generation fills its
+        KV cache from it, halva_amd/decode.py); None on the training path."""
         # every producer kernel writes straight into the (wider) operand buffer of the projection that follows it
         # (norm(x), x') come out of one autograd node so that the residual's gradient is added inside the norm's backward kernel, and
         # x' is a buffer of the block's own: the o / down projections accumulate onto it (no copy of the residual)
         h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, own_x)
         qkv = self.qkv(h, None, use_lora)
         a = K.attention(qkv, info.cos, info.sin, info.seq_start, info.seq_len, self.H, self.D, self.o.in_width, info.branch)
+        if kv_hook is not None:
+            kv_hook(qkv)
         if rows is not None:
             a, x, mine = _take_rows(a, rows), _take_rows(x, rows), RES_INPLACE      # (the gathered residual is a buffer of this block's own)
         x = self.o(a, x, use_lora, mine)
         h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)      # (x is this block's own by now)
+        act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
+        return self.down(act, x, use_lora, mine)
+
+    def decode(self, x, cache, layer_idx, use_lora=True):
+        """One new token per sequence against the KV cache (halva_amd/decode.py), no autograd: x [B, d] (a buffer of the caller's own:
+        the residual adds accumulate onto it) -> [B, d].  The same pieces as forward() - the norms, the LoRA groups with their factors
+        applied unmerged, SwiGLU - with the attention replaced by RoPE + cache append and the split-KV decode kernel."""
+        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, True)
+        qkv = self.qkv(h, None, use_lora)
+        kc, vc = cache.k[layer_idx], cache.v[layer_idx]
+        lens = cache.lens[layer_idx]
+        K.decode_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, self.H, self.D)
+        a = K.decode_attention(qkv, kc, vc, lens, cache.ws, self.H, self.D, self.o.in_width)
+        x = self.o(a, x, use_lora, mine)
+        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)
         act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
         return self.down(act, x, use_lora, mine)
 
@@ -438,19 +457,22 @@ class LlamaModel(nn.Module):
             self._rope[(str(device), n)] = self._rope[key]
         return self._rope[key]
 
-    def run_layers(self, x, seq_start, seq_len, use_lora=True, branch=None, rows=None):
+    def run_layers(self, x, seq_start, seq_len, use_lora=True, branch=None, rows=None, kv_hook=None):
         """x [S, T, d] bf16 -> last hidden state after the final RMSNorm (modelling_llama.py:580-705).
         branch = (br_a, br_b, pos): rows are packed [prefix | A | B] sequences (see halva_sdpa_branch_fwd).
         rows: int64 [n] DISTINCT flat indices into [S * T] of the only hidden rows the caller reads (the DPA loss reads the rows in
         front of a label != -100, halva_trainer.py:522-537): the result is then [n, d] in that order, and the top layer does its
         row-wise part (o projection, MLP, norms) for those rows only - the same arithmetic per row, no row of the reference's
-        [S, T, d] result that anything reads is dropped."""
+        [S, T, d] result that anything reads is dropped.
+        kv_hook: callable(layer index, rotated qkv) - the prompt pass of generation (halva_amd/decode.py:prefill), no autograd."""
         T = x.shape[1]
         cos, sin = self.rope(T, x.device)
         if cos.shape[0] < T:
             self._rope = {}
             cos, sin = self.rope(T, x.device)
         info = SeqInfo(cos, sin, seq_start, seq_len, branch)
+        if kv_hook is not None:
+            return self._prefill_layers(x, info, use_lora, rows, kv_hook)
         hook = self.grad_ready_hook if torch.is_grad_enabled() else None
         for i, layer in enumerate(self.layers):
             if hook is not None and x.requires_grad:
@@ -464,6 +486,19 @@ class LlamaModel(nn.Module):
                 rows = None
             else:
                 x = layer(x, info, use_lora, i > 0)      # from layer 1 on `x` is the previous layer's own output
+        x = self.norm(x)
+        return x if rows is None else x.view(-1, x.shape[-1]).index_select(0, rows)
+
+    def _prefill_layers(self, x, info, use_lora, rows, kv_hook):
+        """run_layers' loop for the prompt pass of generation: each layer hands its rotated qkv to kv_hook(i, qkv)."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("the prompt pass of generation runs under torch.no_grad()")
+        n = len(self.layers)
+        for i, layer in enumerate(self.layers):
+            top = rows if (rows is not None and TOP_ROWS and i == n - 1) else None
+            x = layer(x, info, use_lora, i > 0, top, lambda qkv, i=i: kv_hook(i, qkv))
+            if top is not None:
+                rows = None
         x = self.norm(x)
         return x if rows is None else x.view(-1, x.shape[-1]).index_select(0, rows)
 

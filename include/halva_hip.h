@@ -278,6 +278,33 @@ int halva_phrase_sum_fwd(const float* logp, const int64_t* labels, const int64_t
 int halva_phrase_sum_bwd(const float* dacc, const int64_t* labels, const int64_t* signs, const int64_t* slot_ids, int P,
                          float* dlogp, int B, int T1, void* stream);
 
+/* ---- KV-cached decoding (greedy generation, halva_amd/decode.py).  Cache per layer: kcache, vcache bf16 [B, H, Lcap, D] with D = 128,
+ * lens int32 [B] on the device (the filled slots of row b are [0, lens[b]); no host-side length reaches a launch).
+ *
+ * RoPE + append of the new token.  replaces the decode branch of LlamaAttention.forward: apply_rotary_pos_emb at position
+ * `attention_mask.sum(1) - 1` (llava/model/llava_arch.py:90-98) and `torch.cat([past_key_value[0], key_states], dim=2)` /
+ * the value concat (llava/model/language_model/modelling_llama.py:295-305).  qkv: [B, 3, H, D] rows with stride ldqkv elements (the fused
+ * q|k|v projection).  With p = lens[b]: q of row b rotated in place at position p (halva_rope_qk's arithmetic), the rotated k and the plain
+ * v written to slot p of the cache, then lens[b] = p + 1.  cos / sin: [max_pos, D/2] bf16 (kernels.rope_tables).  A row with
+ * p >= min(Lcap, max_pos) is left untouched (the caller sizes the cache; nothing is written out of bounds). */
+int halva_decode_rope_append(void* qkv, int64_t ldqkv, const void* cos, const void* sin, int max_pos, void* kcache, void* vcache,
+                             int32_t* lens, int B, int H, int D, int Lcap, void* stream);
+/* Single-query attention over the cache.  replaces the decode-time attention of LlamaAttention.forward (modelling_llama.py:307-340:
+ * q_len = 1, softmax(q K^T / sqrt(D)) V over the cached keys).  q: row b, head h at q[b * ldq + h * D] (the rotated q third of the qkv rows);
+ * out: bf16 row b at out[b * ld_out] (the o projection's operand buffer).  fp32 scores, online softmax.  Split KV: one workgroup per
+ * (chunk of KC keys, head, row) writes a partial (m, l, o[D]) in fp32 to `ws`; a second launch combines the ceil(lens[b] / KC) partials of
+ * (b, h) in chunk order.  KC (halva_decode_attn_kc) does not depend on B: row b's output is bitwise the same in any batch.  Slots at or
+ * beyond lens[b] and unused workspace are never read.  scale = 1/sqrt(D) when <= 0.  ws_bytes >= halva_decode_attn_ws_bytes(B, H, Lcap). */
+int halva_decode_attn(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out, int64_t ld_out,
+                      void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, void* stream);
+/* Keys per split-KV chunk of halva_decode_attn (the compile-time constant 256) and its workspace size in bytes (0 for bad sizes). */
+int halva_decode_attn_kc(void);
+int64_t halva_decode_attn_ws_bytes(int B, int H, int Lcap);
+/* Measurement aid (tools/bench_decode.py; no reference counterpart): halva_decode_attn with an explicit chunk of kc = 64, 128 or 256
+ * keys - how the constant above was chosen.  Workspace: B * H * ceil(Lcap / kc) * (D + 2) floats. */
+int halva_decode_attn_chunked(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out,
+                              int64_t ld_out, void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, int kc, void* stream);
+
 /* ---- hardware-layout probes used by the GPU tests (MFMA fragment maps, ds_read_b64_tr_b16). */
 int halva_probe_layouts(int32_t* out, int n, void* stream);
 /* ---- measurement aid (bench.py's clock trace; no reference counterpart): `blocks` one-wave workgroups each spin for `spin_ticks` ticks of

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""KV-cached greedy decoding on a random-weight LLaVA-1.5-7B geometry (32 layers, 32 x 128 heads, LoRA r = 128 unmerged, CLIP ViT-L/14 at
+336 px): prefill ms of one image + 64 text tokens, decode ms per step and tokens/s at B = 1 and B = 16, and the split-KV decode-attention
+kernel alone at B = 16, H = 32, L = 2048 as effective TB/s (bytes = sum_b 2 L_b H D 2) for each chunk size KC.  Not part of bench.py.
+
+    python tools/bench_decode.py [--out profiles/r07_decode.json] [--steps 32]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def _time(fn, reps, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return statistics.median(out)
+
+
+def attn_kernel(kc_values=(64, 128, 256), B=16, H=32, L=2048, D=128, reps=50):
+    from halva_amd import kernels as K
+    dev = "cuda"
+    kc = torch.randn(B, H, L, D, device=dev).to(torch.bfloat16)
+    vc = torch.randn(B, H, L, D, device=dev).to(torch.bfloat16)
+    q = torch.randn(B, 3 * H * D, device=dev).to(torch.bfloat16)
+    lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+    nbytes = 2 * B * L * H * D * 2
+    res = {}
+    for c in kc_values:
+        ws = torch.empty(K.decode_ws_bytes(B, H, L, c), dtype=torch.uint8, device=dev)
+        ms = _time(lambda: K.decode_attention(q, kc, vc, lens, ws, H, D, kc=c), reps, warmup=5)
+        res[str(c)] = {"us": round(ms * 1e3, 2), "TB_s": round(nbytes / (ms * 1e-3) / 1e12, 3)}
+    return {"B": B, "H": H, "L": L, "D": D, "bytes": nbytes, "kc_shipped": K.decode_kc(), "by_kc": res}
+
+
+def model_7b():
+    from halva_amd.llava_model import build_random_llava
+    cfg = dict(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=32, num_attention_heads=32,
+               max_position_embeddings=4096, rms_norm_eps=1e-5, pad_token_id=0)
+    vis = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=336, patch_size=14,
+               layer_norm_eps=1e-5)
+    m = build_random_llava(cfg, vis, lora_r=128, lora_alpha=256, seed=0, device="cuda", max_len=2048)
+    with torch.no_grad():
+        for layer in m.model.layers:
+            for _, grp in layer.groups():
+                grp.weight_cat_t = None          # (training-only copy; inference does not keep it)
+                for Bf in grp._Bs():
+                    Bf.normal_(0.0, 0.02)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    return m
+
+
+def decode_numbers(m, steps):
+    from halva_amd import decode as DEC
+    g = torch.Generator().manual_seed(0)
+    res = {}
+    for B in (1, 16):
+        ids = torch.randint(3, 32000, (B, 64), generator=g)
+        ids[:, 0] = 1
+        ids[:, 6] = -200
+        images = torch.randn(B, 3, 336, 336, generator=g).to("cuda", torch.bfloat16)
+        with torch.no_grad():
+            embeds, plan = m._splice(ids.cuda(), None, None, None, images)
+            T = embeds.shape[1]
+            state = {}
+
+            def do_prefill():
+                state["cache"] = DEC.KVCache(m, B, T + steps + 8)
+                state["logits"] = DEC.prefill(m, embeds, plan.seq_len, state["cache"])
+            pre_ms = _time(do_prefill, 3, warmup=1)
+            tok = state["logits"].argmax(-1)
+
+            def do_steps():
+                cache = state["cache"]
+                cache.lens.copy_(torch.full_like(cache.lens, T))          # every timed pass decodes from the same position
+                cache.filled = T
+                for _ in range(steps):
+                    DEC.decode_step(m, cache, tok)
+            step_ms = _time(do_steps, 3, warmup=1) / steps
+        res["B%d" % B] = {"prompt_rows": T, "prefill_ms": round(pre_ms, 2), "decode_ms_per_step": round(step_ms, 3),
+                          "tokens_per_s": round(B * 1000.0 / step_ms, 1)}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--skip-model", action="store_true")
+    a = ap.parse_args()
+    from halva_amd import hip
+    hip.load()
+    torch.cuda.set_device(0)
+    rec = {"device": torch.cuda.get_device_name(0), "decode_attn": attn_kernel()}
+    if not a.skip_model:
+        m = model_7b()
+        rec["weights_GB"] = round(sum(p.numel() * p.element_size() for n, p in m.named_parameters() if "vision_tower" not in n) / 1e9, 2)
+        rec["decode"] = decode_numbers(m, a.steps)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
