@@ -1,4 +1,4 @@
-"""KV-cached greedy decoding for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) - forward only.
+"""KV-cached greedy decoding for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) and VILA (VilaLlavaLlamaModel.generate) - forward only.
 
 Stands in for the reference's HF `generate(..., use_cache=True)` decode path: the per-layer cache concat
 (llava/model/language_model/modelling_llama.py:295-305) and the decode position rule `attention_mask.sum(1) - 1`
@@ -7,18 +7,31 @@ Stands in for the reference's HF `generate(..., use_cache=True)` decode path: th
 
 Cache layout, per layer: K, V bf16 [B, H, Lcap, D]; lens int32 [layers, B] on the device (each layer's append advances its own
 row).  Prompts are right-padded: sequence b holds positions [0, seq_len[b]).
+
+The functions below run on a DecodeStack (the Llama stack, the lm_head weight, whether the LoRA factors apply).  They also accept either
+model wrapper, which hands over its own pieces through decode_stack(): LLaVA's `.model` / `.lm_head`, VILA's `.llm.model` /
+`.llm.lm_head`.
 """
+from collections import namedtuple
+
 import torch
 
 from . import kernels as K
+
+DecodeStack = namedtuple("DecodeStack", "lm lm_head use_lora")
+DecodeStack.__doc__ = "lm: halva_amd.llama.LlamaModel; lm_head: the [V, d] head weight; use_lora: apply the LoRA factors (unmerged)."
+
+
+def _stack(model):
+    return model if isinstance(model, DecodeStack) else model.decode_stack()
 
 
 class KVCache:
     """[layers][K, V] bf16 [B, H, Lcap, D], lens int32 [layers, B] and the split-KV workspace, allocated once per generate call."""
 
     def __init__(self, model, B, Lcap, device=None):
-        cfg = model.config
-        lm = model.get_model()
+        lm = _stack(model).lm
+        cfg = lm.config
         dev = device or lm.embed_tokens.weight.device
         H = cfg.num_attention_heads
         D = cfg.hidden_size // H
@@ -29,6 +42,8 @@ class KVCache:
         self.lens = torch.zeros(n, B, dtype=torch.int32, device=dev)
         self.filled = 0            # host-side upper bound of max_b lens[b] (no device read): the next append goes to a slot below it + 1
         self.ws = torch.empty(max(K.decode_ws_bytes(B, H, Lcap), 16), dtype=torch.uint8, device=dev)
+        # the append kernel takes the new token's position only through these rows (row p = position p, the linear RoPE scaling of
+        # LlamaModel.rope already applied); they cover every slot of the cache
         cos, sin = lm.rope(Lcap, dev)
         if cos.shape[0] < Lcap:
             lm._rope = {}
@@ -48,15 +63,15 @@ class KVCache:
         self.filled = T
 
 
-def _lm_head(model, h):
-    return torch.nn.functional.linear(h, model.lm_head.weight).float()
+def _lm_head(st, h):
+    return torch.nn.functional.linear(h, st.lm_head).float()
 
 
 @torch.no_grad()
 def prefill(model, inputs_embeds, seq_len, cache):
     """The prompt pass: run_layers on right-padded inputs_embeds [B, T, d] (sequence b = rows [0, seq_len[b])) with the cache fill
     hooked into every layer; the top layer runs only the last prompt row of each sequence.  -> last-row logits [B, V] fp32."""
-    lm = model.get_model()
+    st = _stack(model)
     B, T, _ = inputs_embeds.shape
     dev = inputs_embeds.device
     seq_len = torch.as_tensor(seq_len, dtype=torch.int32)
@@ -64,9 +79,9 @@ def prefill(model, inputs_embeds, seq_len, cache):
         raise ValueError("every prompt needs between 1 and T=%d rows" % T)
     seq_len_d = seq_len.to(dev)
     rows = (torch.arange(B, dtype=torch.int64) * T + seq_len.long() - 1).to(dev)
-    h = lm.run_layers(inputs_embeds.to(torch.bfloat16), torch.zeros(B, dtype=torch.int32, device=dev), seq_len_d, model._use_lora, None, rows,
-                      kv_hook=lambda i, qkv: cache.fill(i, qkv, seq_len_d))
-    return _lm_head(model, h)
+    h = st.lm.run_layers(inputs_embeds.to(torch.bfloat16), torch.zeros(B, dtype=torch.int32, device=dev), seq_len_d, st.use_lora, None,
+                         rows, kv_hook=lambda i, qkv: cache.fill(i, qkv, seq_len_d))
+    return _lm_head(st, h)
 
 
 @torch.no_grad()
@@ -77,8 +92,66 @@ def decode_step(model, cache, token_ids):
         # the new token
         raise RuntimeError("KV cache full: %d slots used of %d; allocate the cache for the prompt plus every new token" % (cache.filled, cache.Lcap))
     cache.filled += 1
-    lm = model.get_model()
+    st = _stack(model)
+    lm = st.lm
     x = lm.embed_tokens(token_ids.to(lm.embed_tokens.weight.device).long())          # a fresh buffer: the residual adds run on it in place
     for i, layer in enumerate(lm.layers):
-        x = layer.decode(x, cache, i, model._use_lora)
-    return _lm_head(model, lm.norm(x))
+        x = layer.decode(x, cache, i, st.use_lora)
+    return _lm_head(st, lm.norm(x))
+
+
+# ------------------------------------------------------------------------------------------------
+# the greedy loop shared by both generate() methods
+def check_greedy_args(num_beams, do_sample, max_new_tokens):
+    """The call the reference's hallucination benchmarks make: do_sample=False, num_beams=1.  Anything else is refused."""
+    if num_beams is not None and num_beams > 1:
+        raise NotImplementedError("generate: beam search (num_beams=%d) is not implemented; greedy decoding only" % num_beams)
+    if do_sample:
+        raise NotImplementedError("generate: sampling (do_sample=True) is not implemented; greedy decoding only")
+    if max_new_tokens is None or max_new_tokens < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+
+
+def eos_and_pad(config, eos_token_id, pad_token_id, device):
+    """-> (EOS ids as a LongTensor, pad id).  EOS: eos_token_id, else config.eos_token_id (an int or a list; [] = none).  Pad:
+    pad_token_id, else config.pad_token_id, else the first EOS id, else 0."""
+    eos = config.eos_token_id if eos_token_id is None else eos_token_id
+    eos_ids = torch.as_tensor([] if eos is None else ([eos] if isinstance(eos, int) else list(eos)), dtype=torch.long, device=device)
+    pad = pad_token_id if pad_token_id is not None else getattr(config, "pad_token_id", None)
+    pad = pad if pad is not None else (int(eos_ids[0]) if eos_ids.numel() else 0)
+    return eos_ids, pad
+
+
+@torch.no_grad()
+def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria=None, prefix=None):
+    """Prefill, then argmax -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
+
+    A row that emitted an id of eos_ids is done and gets `pad` from then on.  stopping_criteria: a callable or a list of them (HF
+    StoppingCriteriaList semantics: any criterion that returns True stops the batch; a tensor it returns marks rows done), each called
+    after every step as criterion(seq, logits) with seq = cat(prefix, new tokens), or the new tokens alone when prefix is None.
+    One host sync per step."""
+    dev = inputs_embeds.device
+    B = inputs_embeds.shape[0]
+    crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
+    cache = KVCache(model, B, inputs_embeds.shape[1] + max_new_tokens, dev)
+    logits = prefill(model, inputs_embeds, seq_len, cache)
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    out = []
+    for step in range(max_new_tokens):
+        nxt = logits.argmax(-1)
+        nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
+        out.append(nxt)
+        if eos_ids.numel():
+            done = done | torch.isin(nxt, eos_ids)
+        if crits:
+            seq = torch.stack(out, 1) if prefix is None else torch.cat([prefix, torch.stack(out, 1)], 1)
+            for crit in crits:
+                stop = crit(seq, logits)
+                if isinstance(stop, torch.Tensor):
+                    done = done | stop.to(dev, torch.bool).view(-1).expand(B)
+                elif stop:
+                    done = torch.ones_like(done)
+        if step + 1 == max_new_tokens or bool(done.all()):          # the step's one host sync
+            break
+        logits = decode_step(model, cache, nxt)
+    return torch.stack(out, 1)

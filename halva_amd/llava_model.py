@@ -289,6 +289,11 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
         return CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
 
     # -- generation ------------------------------------------------------------------------------
+    def decode_stack(self):
+        """The pieces the KV-cached decode runs on (halva_amd/decode.py)."""
+        from .decode import DecodeStack
+        return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
+
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
                  max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, image_sizes=None,
@@ -299,14 +304,9 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
         (fp16 accepted).  Returns LongTensor [B, T + n]: the prompt as given, then the new tokens; a row that emitted EOS is padded
         with pad_token_id after it.  Stops when every row is done or after max_new_tokens; one host sync per step."""
         from . import decode as DEC
-        if num_beams is not None and num_beams > 1:
-            raise NotImplementedError("generate: beam search (num_beams=%d) is not implemented; greedy decoding only" % num_beams)
-        if do_sample:
-            raise NotImplementedError("generate: sampling (do_sample=True) is not implemented; greedy decoding only")
+        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
         if input_ids is None or input_ids.ndim != 2:
             raise ValueError("generate needs input_ids [B, T]")
-        if max_new_tokens is None or max_new_tokens < 1:
-            raise ValueError("max_new_tokens must be >= 1")
         dev = self.device
         prompt = input_ids
         ids = input_ids.to(dev)
@@ -330,32 +330,9 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
                 seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
         if int(seq_start.max()) != 0:
             raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
-        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
-        eos_ids = torch.as_tensor([] if eos is None else ([eos] if isinstance(eos, int) else list(eos)), dtype=torch.long, device=dev)
-        pad = pad_token_id if pad_token_id is not None else getattr(self.config, "pad_token_id", None)
-        pad = pad if pad is not None else (int(eos_ids[0]) if eos_ids.numel() else 0)
-        T = embeds.shape[1]
-        cache = DEC.KVCache(self, B, T + max_new_tokens, dev)
-        logits = DEC.prefill(self, embeds, seq_len, cache)
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
-        out = []
-        for step in range(max_new_tokens):
-            nxt = logits.argmax(-1)
-            nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
-            out.append(nxt)
-            if eos_ids.numel():
-                done = done | torch.isin(nxt, eos_ids)
-            if stopping_criteria is not None:
-                seq = torch.cat([prompt.to(dev), torch.stack(out, 1)], 1)
-                stop = stopping_criteria(seq, logits)
-                if isinstance(stop, torch.Tensor):
-                    done = done | stop.to(dev, torch.bool).view(-1).expand(B)
-                elif stop:
-                    done = torch.ones_like(done)
-            if step + 1 == max_new_tokens or bool(done.all()):          # the step's one host sync
-                break
-            logits = DEC.decode_step(self, cache, nxt)
-        return torch.cat([prompt.to(dev).long(), torch.stack(out, 1)], 1)
+        eos_ids, pad = DEC.eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
+        out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt.to(dev))
+        return torch.cat([prompt.to(dev).long(), out], 1)
 
     __call__ = nn.Module.__call__
 

@@ -421,6 +421,57 @@ class VilaLlavaLlamaModel(nn.Module):
         return CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None,
                               labels=labels, signs=signs)
 
+    # -- generation (llava_llama.py:180-206) ------------------------------------------------------
+    def decode_stack(self):
+        """The pieces the KV-cached decode runs on (halva_amd/decode.py): the `.llm`'s Llama stack and head."""
+        from .decode import DecodeStack
+        return DecodeStack(self.llm.model, self.llm.lm_head.weight, self._use_lora)
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
+                 max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, **unused):
+        """Greedy decoding with a KV cache: the call of the reference's VILA hallucination benchmarks (eval_hall_vila/*: do_sample=False,
+        temperature=0, num_beams=1, use_cache=True, stopping_criteria None or [KeywordsStoppingCriteria]).
+        input_ids [B, T] (IMAGE_TOKEN_INDEX marks each image; right-padded batches carry attention_mask); images [B, 3, H, W], a list of
+        them or [B, n, 3, H, W] (fp16 accepted).  The splice is prepare_inputs_labels_for_multimodal's; the prompt pass and the decode
+        steps run on `.llm` (halva_amd/decode.py:greedy).
+
+        Returns LongTensor [B, n]: the NEW tokens only, without the prompt - the reference hands the spliced inputs_embeds to
+        `self.llm.generate`, which returns only the generated ids then (and the eval scripts decode output_ids whole).  LLaVA's generate
+        returns [B, T + n] instead.  A row that emitted EOS is padded with pad_token_id after it; the loop stops when every row is done
+        or after max_new_tokens.  stopping_criteria (a callable or a list of them; any True stops the batch) see the new tokens only,
+        as HF hands them over for inputs_embeds generation."""
+        from . import decode as DEC
+        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
+        if input_ids is None or input_ids.ndim != 2:
+            raise ValueError("generate needs input_ids [B, T]")
+        dev = self.device
+        ids = input_ids.to(dev)
+        mask = None if attention_mask is None else attention_mask.to(dev)
+        B, T0 = ids.shape
+        if mask is not None and int(SP.spans_from_mask(_cpu(mask))[0].max()) != 0:
+            # (the splice would re-pad such rows to the right; the contract is the LLaVA one: right padding only)
+            raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
+        embeds = None
+        if images is not None:
+            images = [im.to(dev, torch.bfloat16) for im in images] if type(images) is list else images.to(dev, torch.bfloat16)
+            self._last_plan = None
+            _, _, _, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, images)
+        if embeds is not None:
+            seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len
+        else:
+            if (ids < 0).any():
+                raise ValueError("input_ids hold image tokens but no images (or no vision tower) were given")
+            embeds = self.llm.model.embed_tokens(ids)
+            if mask is None:
+                seq_start, seq_len = torch.zeros(B, dtype=torch.int32), torch.full((B,), T0, dtype=torch.int32)
+            else:
+                seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
+        if int(seq_start.max()) != 0:
+            raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
+        eos_ids, pad = DEC.eos_and_pad(self.llm.config, eos_token_id, pad_token_id, dev)
+        return DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=None)
+
 
 def _load_tokenizer(llm_path, model_max_length):
     """language_model/builder.py:83-114: slow Llama tokenizer, right padding, legacy=False."""

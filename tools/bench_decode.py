@@ -3,7 +3,11 @@
 336 px): prefill ms of one image + 64 text tokens, decode ms per step and tokens/s at B = 1 and B = 16, and the split-KV decode-attention
 kernel alone at B = 16, H = 32, L = 2048 as effective TB/s (bytes = sum_b 2 L_b H D 2) for each chunk size KC.  Not part of bench.py.
 
-    python tools/bench_decode.py [--out profiles/r07_decode.json] [--steps 32]
+--model vila13b: the VILA-13B geometry instead (40 layers, 40 x 128 heads, d = 5120, F = 13824, LoRA r = 128 unmerged, SigLIP-so400m at
+384 px -> 196 image tokens after mlp_downsample, linear RoPE factor 2): one image + 60 text tokens, the attention kernel at H = 40,
+L = 4096.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -66,15 +70,31 @@ def model_7b():
     return m
 
 
-def decode_numbers(m, steps):
+def model_vila13b():
+    import bench
+    from halva_amd.vila_model import build_random_vila
+    cfg = dict(bench.LLAMA_13B, rope_scaling={"type": "linear", "factor": 2.0})
+    m = build_random_vila(cfg, dict(bench.SIGLIP_SO400M_384), lora_r=128, lora_alpha=256, seed=0, device="cuda", max_len=4096)
+    with torch.no_grad():
+        for layer in m.llm.model.layers:
+            for _, grp in layer.groups():
+                grp.weight_cat_t = None
+                for Bf in grp._Bs():
+                    Bf.normal_(0.0, 0.02)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    return m
+
+
+def decode_numbers(m, steps, text=64, image=336):
     from halva_amd import decode as DEC
     g = torch.Generator().manual_seed(0)
     res = {}
     for B in (1, 16):
-        ids = torch.randint(3, 32000, (B, 64), generator=g)
+        ids = torch.randint(3, 32000, (B, text), generator=g)
         ids[:, 0] = 1
         ids[:, 6] = -200
-        images = torch.randn(B, 3, 336, 336, generator=g).to("cuda", torch.bfloat16)
+        images = torch.randn(B, 3, image, image, generator=g).to("cuda", torch.bfloat16)
         with torch.no_grad():
             embeds, plan = m._splice(ids.cuda(), None, None, None, images)
             T = embeds.shape[1]
@@ -103,15 +123,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--model", choices=("llava7b", "vila13b"), default="llava7b")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
     torch.cuda.set_device(0)
-    rec = {"device": torch.cuda.get_device_name(0), "decode_attn": attn_kernel()}
+    vila = a.model == "vila13b"
+    rec = {"device": torch.cuda.get_device_name(0), "model": a.model,
+           "decode_attn": attn_kernel(H=40, L=4096) if vila else attn_kernel()}
     if not a.skip_model:
-        m = model_7b()
+        m = model_vila13b() if vila else model_7b()
         rec["weights_GB"] = round(sum(p.numel() * p.element_size() for n, p in m.named_parameters() if "vision_tower" not in n) / 1e9, 2)
-        rec["decode"] = decode_numbers(m, a.steps)
+        rec["decode"] = decode_numbers(m, a.steps, text=60, image=384) if vila else decode_numbers(m, a.steps)
     line = json.dumps(rec)
     print(line)
     if a.out:
