@@ -51,7 +51,7 @@ __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w 
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 __device__ __forceinline__ float bf16_round(float f) { return bf16_to_f32(f32_to_bf16(f)); }
 
-// One RoPE pair, rope_qk_kernel's arithmetic (rowops.hip) - shared with the attention backward's store epilogues (sdpa.hip), which apply
+// One RoPE pair, rope_qk_kernel's arithmetic (rowops.hip) - shared with the attention backward's store epilogues (sdpa_common.h, sdpa_dkv3.h), which apply
 // the INVERSE rotation (s = -sin) to the freshly rounded dq / dk rows: x1, x2 = elements d and d + D/2 of a head row, already bf16 values.
 template <class T>      // float, or a pair of floats (ext_vector_type(2): v_pk_mul_f32 / v_pk_fma_f32 - half the instructions, the same values)
 __device__ __forceinline__ void rope_pair(T x1, T x2, T c, T s, T& y1, T& y2) {

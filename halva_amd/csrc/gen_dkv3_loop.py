@@ -49,7 +49,7 @@ SRC = (98, 99)
 # Q / dO tiles arrive through bounds-checked buffer descriptors over the sequence's rows of this head (round 4: as sdpa_fwd3's K / V tiles): a row past
 # the sequence arrives as ZEROS (experiments/fwd3/oob_probe.hip), so the partial last tile and the requests past the block's end need no case of
 # their own - three instructions per 1-KiB piece instead of ten.  The statistics (round 4, second pass): the delta kernel writes lse2 and -delta of a
-# 64-row step side by side - [lse2 x 64][-delta x 64] = 512 bytes per step, steps in sequence coordinates (sdpa.hip:sdpa_bwd_delta_kernel) - so ONE
+# 64-row step side by side - [lse2 x 64][-delta x 64] = 512 bytes per step, steps in sequence coordinates (sdpa_bwd_dq2.h:sdpa_bwd_delta_kernel) - so ONE
 # `buffer_load_dwordx4 ... lds` per step brings both (lanes 0..31; the upper lanes' offsets lie outside the descriptor and write zeros into the unused
 # half of the 1-KiB statistics slot), a step past the sequence brings zeros, and the selects, the dummy target and the clamped-lane path of the two
 # pointer-form requests are gone: 4 instructions instead of 18 + 6, one vector-memory operation instead of two (a request costs the lone wave ~25-60
@@ -67,7 +67,7 @@ WAIT_GAP = 64 - LOOKAHEAD - 1
 CTL_NPRO, CTL_PROALT = "s_bfe_u32 s97, %[ctl], 0x20001", "s_bfe_u32 s97, %[ctl], 0x30003"
 # Round 6: the ITEM RECORD.  Everything about an item (sequence, head, key block) that is uniform over the workgroup - its geometry, the run lengths
 # of its first call, the bases / extents of its buffer descriptors, its dS strip, its K / dK rows - is worked out ONCE, by the delta pass of the same
-# C-ABI call (sdpa.hip:dkv3_build_record), as 64 dwords in queue order.  A wave holds an item's record in ONE vector register (lane l = dword l,
+# C-ABI call (sdpa_dkv3_items.h:dkv3_build_record), as 64 dwords in queue order.  A wave holds an item's record in ONE vector register (lane l = dword l,
 # a ds_read_b32 of the workgroup's mail box) and the block picks its fields with v_readlane_b32; before, ~1 450 compiler instructions per item
 # re-derived them (profiles/r06_dkv3_anatomy.log: 6 600 cycles in front of every block with nothing to overlap them).  REC: dword index by name.
 REC_FIELDS = ["valid", "s", "hd", "kb", "start", "len", "br_a", "br_b", "kblk_min", "q_begin", "ntiles", "last_partial", "lr", "prefetchable",

@@ -58,7 +58,7 @@ O_STORE_POLICY = " nt" if os.environ.get("FWD3_O_NT", "0") == "1" else ""      #
 WAIT_AGE = int(os.environ.get("FWD3_WAIT_AGE", "4"))      # 0: one wait per first use
 # 2^100, 120.0, repeats at most: 64 x 120 log2 units = scores 5 300 nats above the row's first keys (round 5; 8 before: round-4 advice).  A bound there must
 # be: NaN / inf scores overflow on every pass.  Rows beyond it come back as NaN (l = inf) - loudly, not as wrong numbers - unless the launch is followed
-# by the running-maximum kernel in repair mode (sdpa.hip: SdpaParams::repair, HALVA_FWD3_REPAIR=1).
+# by the running-maximum kernel in repair mode (sdpa_common.h: SdpaParams::repair; sdpa_fwd.h; HALVA_FWD3_REPAIR=1).
 REDO_LIMIT, REDO_STEP, MAX_REDO = 0x71800000, 0x42f00000, 64
 XS = {(0, 0): 64, (0, 1): 80, (1, 0): 96, (1, 1): 112}      # score tiles [group][key half]: 16 registers each
 PB = {(0, 0): 128, (0, 1): 136, (1, 0): 144, (1, 1): 152}   # packed P: 8 registers each

@@ -1,6 +1,6 @@
 // sdpa_bwd_dkv3: dK / dV (+ dS store) with ONE wave per SIMD - included by sdpa.hip inside its anonymous namespace (head_dim 128 only).
 //
-// Replaces sdpa_bwd_dkv2 on the dS-workspace path of halva_sdpa_branch_bwd_ws (the backward of flash_attn_varlen_qkvpacked_func,
+// Replaces sdpa_bwd_dkv2 (sdpa_bwd_dkv2.h) on the dS-workspace path of halva_sdpa_branch_bwd_ws (the backward of flash_attn_varlen_qkvpacked_func,
 // reference llava/train/llama_flash_attn_monkey_patch.py:85-91).  Why another structure: the two-role kernel puts two 256-register waves
 // on every SIMD and they meet - at the matrix pipe, in their vector stretches and at the step's barrier - in lock step: ~3 850 cycles
 // per 64-row step for 2 048 cycles of matrix work, whatever was done to either wave's own stream.  Here a workgroup is

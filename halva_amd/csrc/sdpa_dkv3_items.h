@@ -5,7 +5,7 @@
 // (sequence, head, key block) with three divisions, looked the sequence up, posted eight words to an LDS mail box; every wave collected them, redid
 // the geometry, the run lengths of the masked / plain / masked phases, eight 64-bit base addresses, the extents of three buffer descriptors -
 // ~1 450 instructions at 4-5 cycles each = 6 600 cycles in front of every generated block (profiles/r06_dkv3_anatomy.log).
-// All of it is a function of the launch parameters and the item's index alone, so the delta pass of the SAME C-ABI call (sdpa_bwd_delta_kernel, which
+// All of it is a function of the launch parameters and the item's index alone, so the delta pass of the SAME C-ABI call (sdpa_bwd_delta_kernel in sdpa_bwd_dq2.h, which
 // runs first anyway) now writes it once, as one 256-byte record per item in queue order; the workgroups fetch a record with one 16-lane load inside
 // the generated block (under a wait that exists anyway), hand it round through LDS and pick fields with v_readlane_b32.
 // Replaces (with sdpa_dkv3.h) the backward of flash_attn_varlen_qkvpacked_func, reference llava/train/llama_flash_attn_monkey_patch.py:85-91.

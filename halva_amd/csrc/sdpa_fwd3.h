@@ -1,6 +1,6 @@
 // sdpa_fwd3: the causal forward (head_dim 128) with ONE wave per SIMD - included by sdpa.hip inside its anonymous namespace.
 //
-// Replaces sdpa_fwd_kernel<128, true> for flash_attn_varlen_qkvpacked_func's forward (reference llava/train/llama_flash_attn_monkey_patch.py:85-91).
+// Replaces sdpa_fwd_kernel<128, true> (sdpa_fwd.h) for flash_attn_varlen_qkvpacked_func's forward (reference llava/train/llama_flash_attn_monkey_patch.py:85-91).
 // Why another structure: sdpa_fwd_kernel puts two 256-register waves of 32 query rows on every SIMD; they meet at the matrix pipe, in
 // their softmax stretches and at the tile's barrier in lock step: ~5 100 cycles per 64 MFMAs and SIMD for 2 048 cycles of matrix work (DESIGN
 // 6, 6b).  Here a workgroup is 4 waves = 256 query rows, a wave owns 64 rows (two groups of 32) with the Q fragments (64 registers) and the
@@ -15,7 +15,7 @@
 // the row SUMS: a partial sum not below 2^100 repeats the WHOLE row block, inside the same asm block, with the reference of those rows raised
 // by 120, at most MAX_REDO = 64 times (gen_fwd3_loop.py; test_sdpa_exponent_reference_moves_when_later_keys_dominate).  A finite row whose
 // maximum lies further out than 64 x 120 log2 units (~5 300 nats above its first keys) leaves this kernel with l = inf: NaN output rows, lse = inf -
-// loud, not silently wrong.  HALVA_FWD3_REPAIR=1 makes launch_fwd follow every sdpa_fwd3 launch with the running-maximum kernel in repair mode
+// loud, not silently wrong.  HALVA_FWD3_REPAIR=1 makes sdpa.hip (choose_fwd) follow every sdpa_fwd3 launch with the running-maximum kernel in repair mode
 // (SdpaParams::repair), which redoes exactly the row blocks that hold a non-finite lse with no bound at all (as flash-attn); it is OFF by default:
 // the pass costs ~30 us per launch (4 % of the forward: 2 048 workgroups that each read their lse rows and leave) for inputs no training run produces
 // (test_sdpa_forward_far_beyond_the_repeat_budget_is_repaired).

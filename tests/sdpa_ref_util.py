@@ -1,4 +1,4 @@
-"""Plain-torch references for the fused attention kernels (halva_amd/csrc/sdpa.hip), for row-wise checks.
+"""Plain-torch references for the fused attention kernels (halva_amd/csrc/sdpa.hip and its sdpa_*.h), for row-wise checks.
 
 Two restatements of one computation - causal varlen attention with the branch mask of halva_sdpa_branch_fwd (include/halva_hip.h),
 the semantics of flash_attn_varlen_qkvpacked_func + unpad_input / pad_input (reference llama_flash_attn_monkey_patch.py:71-91):

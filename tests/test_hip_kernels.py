@@ -395,7 +395,7 @@ def test_sdpa_exponent_reference_moves_when_later_keys_dominate(D):
 def test_sdpa_forward_far_beyond_the_repeat_budget_is_repaired(scale_last, monkeypatch):
     """Round-4 advice: sdpa_fwd3 repeated a row block at most 8 times (+120 log2 units each: 660 nats); now 64 times (5 300 nats).  A FINITE row whose
     maximum lies further out than that - here ~22 000 nats above its first 32 keys - comes back as NaN (loud), and with HALVA_FWD3_REPAIR=1 the launch
-    is followed by the running-maximum kernel in repair mode (sdpa.hip: SdpaParams::repair), which redoes exactly the row blocks that hold a
+    is followed by the running-maximum kernel in repair mode (sdpa_common.h: SdpaParams::repair, sdpa_fwd.h), which redoes exactly the row blocks that hold a
     non-finite lse.  Rows ~2 200 nats out (the old failure) are handled by the kernel itself."""
     T, H, S, D = 256, 2, 1, 128
     g = torch.Generator().manual_seed(12)

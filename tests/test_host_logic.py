@@ -200,7 +200,7 @@ def test_bench_visible_pairs_counts_what_the_branch_mask_lets_through():
 
 
 def test_tile_dma_source_swizzle_inverts_the_lds_tile_layout():
-    """csrc/sdpa.hip: an LDS-DMA request writes 1 KiB at (wave-uniform base + 16 * lane), so lane l of chunk c must FETCH the 16 bytes
+    """csrc/sdpa_common.h: an LDS-DMA request writes 1 KiB at (wave-uniform base + 16 * lane), so lane l of chunk c must FETCH the 16 bytes
     whose tile_off is 1024 c + 16 l (stage_tile_dma / TileDma::init).  Integer mirror of both formulas: the source map is the exact
     inverse of tile_off, a bijection onto the tile, and a wave's chunks differ by whole rows (what lets one lane offset serve them)."""
     for D in (128, 64):

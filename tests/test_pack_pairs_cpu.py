@@ -55,7 +55,7 @@ def test_pack_pairs_truncated_rows():
 
 def test_positions_follow_from_the_branch_points():
     """halva_sdpa_branch_bwd_rope / halva_rope_qk_branch (round 5) take no position table: row t of a packed row sits at position t, and at
-    br_a + (t - br_b) once t >= br_b (csrc/sdpa.hip:rope_position).  That must be what pack_pairs writes into `pos` for EVERY row that carries a
+    br_a + (t - br_b) once t >= br_b (csrc/sdpa_common.h:rope_position).  That must be what pack_pairs writes into `pos` for EVERY row that carries a
     token (the padding rows between the correct rest and br_b carry zero vectors: their gradients are exactly zero, their position is immaterial)."""
     rng = np.random.default_rng(5)
     for trial in range(20):

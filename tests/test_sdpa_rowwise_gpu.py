@@ -32,7 +32,7 @@ are real query rows of the packed computation (what splice.pack_pairs writes the
 NaN, and P o (dP - delta) carries it into the prefix keys' dK even with dO = 0 on those rows.  Non-finite values there are a forward
 question only (its valid rows never see them): test_forward_with_nonfinite_branch_padding, a strict xfail that states the gap.
 
-Paths are selected per call (environment switches read on every launch, sdpa.hip launch_fwd / launch_bwd); entry points go through
+Paths are selected per call (environment switches read on every launch, sdpa.hip read_switches / choose_fwd / choose_bwd); entry points go through
 the C ABI (halva_amd.hip.call) directly.
 """
 import math

@@ -1,4 +1,5 @@
-"""Build-time check of sdpa_bwd_dkv3's generated-asm kernel (device assembly from `hipcc -S --cuda-device-only sdpa.hip`):
+"""Build-time check of sdpa_bwd_dkv3's generated-asm kernel (device assembly from `hipcc -S --cuda-device-only sdpa.hip`, the
+translation unit that includes the kernel's header sdpa_dkv3.h):
   * no compiler-generated instruction touches a128-a191 (the K / V fragments are fetched by hand into those registers and may still be in
     flight while the compiler's code runs: a copy would read them too early);
   * no scratch (a scratch reload waits, in order, for every tile request in flight);

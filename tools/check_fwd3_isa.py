@@ -1,4 +1,5 @@
-"""Build-time check of sdpa_fwd3's generated-asm kernel (device assembly from `hipcc -S --cuda-device-only sdpa.hip`):
+"""Build-time check of sdpa_fwd3's generated-asm kernel (device assembly from `hipcc -S --cuda-device-only sdpa.hip`, the
+translation unit that includes the kernel's header sdpa_fwd3.h):
   * no compiler-generated instruction touches a128-a191: the Q fragments are fetched by hand into those registers (behind a block, for the NEXT
     row block) and may still be in flight while the compiler's code runs - a copy would read them too early;
   * no compiler-generated wait for vector memory (s_waitcnt vmcnt) and no vector load outside the asm statements on the common path: the compiler
