@@ -39,15 +39,47 @@ class CLIPVisionConfig:
         return {k: getattr(self, k) for k in self._defaults}
 
 
-class _ClipLayer(nn.Module):
-    def __init__(self, cfg, dtype, device):
+class ViTLayer(nn.Module):
+    """The twelve tensors of one pre-LN ViT block.  head_pad > head_dim: every head runs zero-padded to head_pad lanes (the
+    attention kernel has 64/128-wide tiles) - the q/k/v rows and out_proj columns of the pad lanes are zero."""
+
+    def __init__(self, cfg, dtype, device, head_pad=None):
         super().__init__()
-        d, f = cfg.hidden_size, cfg.intermediate_size
+        d, f, H = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        hd = d if head_pad is None else H * head_pad
         mk = lambda *s: nn.Parameter(torch.zeros(*s, dtype=dtype, device=device), requires_grad=False)
         self.ln1_w, self.ln1_b, self.ln2_w, self.ln2_b = mk(d), mk(d), mk(d), mk(d)
-        self.qkv_w, self.qkv_b = mk(3 * d, d), mk(3 * d)          # fused [q;k;v]
-        self.out_w, self.out_b = mk(d, d), mk(d)
+        self.qkv_w, self.qkv_b = mk(3 * hd, d), mk(3 * hd)          # fused [q;k;v]
+        self.out_w, self.out_b = mk(d, hd), mk(d)
         self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b = mk(f, d), mk(f), mk(d, f), mk(d)
+
+    def load_hf(self, sd, p, H, D):
+        """HF encoder-layer names under prefix `p` (CLIP and SigLIP share them); D = the checkpoint's head width."""
+        d, Dp = self.out_w.shape[0], self.out_w.shape[1] // H
+        self.ln1_w.copy_(sd[p + "layer_norm1.weight"]), self.ln1_b.copy_(sd[p + "layer_norm1.bias"])
+        self.ln2_w.copy_(sd[p + "layer_norm2.weight"]), self.ln2_b.copy_(sd[p + "layer_norm2.bias"])
+        self.qkv_w.zero_(), self.qkv_b.zero_(), self.out_w.zero_()              # the pad lanes stay exactly zero
+        for j, n in enumerate(("q_proj", "k_proj", "v_proj")):
+            self.qkv_w.view(3, H, Dp, d)[j, :, :D].copy_(sd[p + "self_attn.%s.weight" % n].reshape(H, D, d))
+            self.qkv_b.view(3, H, Dp)[j, :, :D].copy_(sd[p + "self_attn.%s.bias" % n].reshape(H, D))
+        self.out_w.view(d, H, Dp)[:, :, :D].copy_(sd[p + "self_attn.out_proj.weight"].reshape(d, H, D))
+        self.out_b.copy_(sd[p + "self_attn.out_proj.bias"])
+        self.fc1_w.copy_(sd[p + "mlp.fc1.weight"]), self.fc1_b.copy_(sd[p + "mlp.fc1.bias"])
+        self.fc2_w.copy_(sd[p + "mlp.fc2.weight"]), self.fc2_b.copy_(sd[p + "mlp.fc2.bias"])
+
+
+def run_vit_blocks(x, layers, H, head_width, scale, eps, act):
+    """`layers` pre-LN transformer blocks on x [N, S, d].  head_width: the (padded) lanes per head of the fused qkv; scale 0 =
+    1/sqrt(head_width); act: the MLP activation, a callable on the fc1 output (it may work in place)."""
+    for L in layers:
+        h = K.layernorm(x, L.ln1_w, L.ln1_b, eps)
+        qkv = F.linear(h, L.qkv_w, L.qkv_b)
+        a = K.sdpa_full(qkv, H, head_width, scale)
+        x = x + F.linear(a, L.out_w, L.out_b)
+        h = K.layernorm(x, L.ln2_w, L.ln2_b, eps)
+        h = act(F.linear(h, L.fc1_w, L.fc1_b))
+        x = x + F.linear(h, L.fc2_w, L.fc2_b)
+    return x
 
 
 class CLIPVisionTower(nn.Module):
@@ -80,7 +112,11 @@ class CLIPVisionTower(nn.Module):
         self.class_embedding = mk(d)
         self.position_embedding = mk((cfg.image_size // p) ** 2 + 1, d)
         self.pre_ln_w, self.pre_ln_b = mk(d), mk(d)
-        self.layers = nn.ModuleList([_ClipLayer(cfg, dtype, device) for _ in range(cfg.num_hidden_layers)])
+        self.layers = nn.ModuleList([ViTLayer(cfg, dtype, device) for _ in range(cfg.num_hidden_layers)])
+
+    def _load_processor(self):
+        from transformers import CLIPImageProcessor
+        return CLIPImageProcessor.from_pretrained(self.vision_tower_name)
 
     def load_model(self, state_dict=None):
         if not hasattr(self, "layers"):
@@ -88,14 +124,24 @@ class CLIPVisionTower(nn.Module):
         if state_dict is None and self.vision_tower_name and os.path.isdir(str(self.vision_tower_name)):
             state_dict = _read_checkpoint(self.vision_tower_name)
             try:
-                from transformers import CLIPImageProcessor
-                self.image_processor = CLIPImageProcessor.from_pretrained(self.vision_tower_name)
+                self.image_processor = self._load_processor()
             except Exception:
                 self.image_processor = None
         if state_dict is not None:
             self.load_hf_state_dict(state_dict)
         self.requires_grad_(False)
         self.is_loaded = True
+
+    def _n_run(self):
+        """Only the blocks that feed `hidden_states[select_layer]` run."""
+        return self._cfg.num_hidden_layers + 1 + self.select_layer if self.select_layer < 0 else self.select_layer
+
+    def _load_layers(self, sd, head_dim):
+        H = self._cfg.num_attention_heads
+        for i, L in enumerate(self.layers):
+            p = "encoder.layers.%d." % i
+            if p + "layer_norm1.weight" in sd:
+                L.load_hf(sd, p, H, head_dim)
 
     def load_hf_state_dict(self, sd):
         """HF CLIPVisionModel names, with or without the `vision_model.` prefix."""
@@ -109,19 +155,7 @@ class CLIPVisionTower(nn.Module):
             self.position_embedding.copy_(sd["embeddings.position_embedding.weight"])
             self.pre_ln_w.copy_(sd["pre_layrnorm.weight"])
             self.pre_ln_b.copy_(sd["pre_layrnorm.bias"])
-            d = cfg.hidden_size
-            for i, L in enumerate(self.layers):
-                p = "encoder.layers.%d." % i
-                if p + "layer_norm1.weight" not in sd:
-                    continue
-                L.ln1_w.copy_(sd[p + "layer_norm1.weight"]), L.ln1_b.copy_(sd[p + "layer_norm1.bias"])
-                L.ln2_w.copy_(sd[p + "layer_norm2.weight"]), L.ln2_b.copy_(sd[p + "layer_norm2.bias"])
-                for j, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                    L.qkv_w[j * d:(j + 1) * d].copy_(sd[p + "self_attn.%s.weight" % n])
-                    L.qkv_b[j * d:(j + 1) * d].copy_(sd[p + "self_attn.%s.bias" % n])
-                L.out_w.copy_(sd[p + "self_attn.out_proj.weight"]), L.out_b.copy_(sd[p + "self_attn.out_proj.bias"])
-                L.fc1_w.copy_(sd[p + "mlp.fc1.weight"]), L.fc1_b.copy_(sd[p + "mlp.fc1.bias"])
-                L.fc2_w.copy_(sd[p + "mlp.fc2.weight"]), L.fc2_b.copy_(sd[p + "mlp.fc2.bias"])
+            self._load_layers(sd, cfg.hidden_size // cfg.num_attention_heads)
 
     # -- forward ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -139,16 +173,8 @@ class CLIPVisionTower(nn.Module):
         x = K.clip_patch_embed(x, self.patch_w, cfg.patch_size, d)
         x = torch.cat([self.class_embedding.expand(N, 1, d), x], 1) + self.position_embedding[None]
         x = K.layernorm(x.contiguous(), self.pre_ln_w, self.pre_ln_b, eps)
-        n_run = cfg.num_hidden_layers + 1 + self.select_layer if self.select_layer < 0 else self.select_layer
-        for L in list(self.layers)[:n_run]:
-            h = K.layernorm(x, L.ln1_w, L.ln1_b, eps)
-            qkv = F.linear(h, L.qkv_w, L.qkv_b)
-            a = K.sdpa_full(qkv, H, d // H)
-            x = x + F.linear(a, L.out_w, L.out_b)
-            h = K.layernorm(x, L.ln2_w, L.ln2_b, eps)
-            h = F.linear(h, L.fc1_w, L.fc1_b)
-            h = K.quick_gelu_(h)                      # h * sigmoid(1.702 h), CLIPMLP's quick_gelu, in place
-            x = x + F.linear(h, L.fc2_w, L.fc2_b)
+        # quick_gelu_: h * sigmoid(1.702 h), CLIPMLP's quick_gelu, in place
+        x = run_vit_blocks(x, list(self.layers)[:self._n_run()], H, d // H, 0.0, eps, K.quick_gelu_)
         if self.select_feature == "patch":
             return x[:, 1:]
         if self.select_feature == "cls_patch":

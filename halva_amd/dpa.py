@@ -18,7 +18,6 @@ import math
 import os
 import warnings
 
-from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -255,14 +254,9 @@ def _distinct_rows(hid, dev):
 
 def model_spec(model):
     """What the step planner needs to know about a model wrapper: image tokens per image after the projector, the
-    post-splice truncation length and padding side, and whether an image-less row advances the image index.
-    LlavaLlamaForCausalLM (llava path) is described here; the VILA wrapper supplies its own `dpa_spec()`."""
-    if hasattr(model, "dpa_spec"):
-        return model.dpa_spec()
-    cfg = model.config
-    return SimpleNamespace(n_patch=model.get_vision_tower().num_patches,
-                           max_len=getattr(cfg, "tokenizer_model_max_length", None),
-                           padding_side=getattr(cfg, "tokenizer_padding_side", "right"), imageless_consumes=True)
+    post-splice truncation length and padding side, and whether an image-less row advances the image index
+    (halva_amd/multimodal.py:dpa_spec, answered by both wrappers)."""
+    return model.dpa_spec()
 
 
 class DPAEngine:
@@ -468,13 +462,12 @@ class FlatTrainables:
 
 def _llm_of(model):
     """(causal LM holding `.model.layers`, name prefix): the LLaVA wrapper IS the LM, VILA keeps it under `.llm`."""
-    return (model.get_llm(), "llm.") if hasattr(model, "get_llm") else (model, "")
+    return model.causal_lm()
 
 
 def _projector_of(model):
-    if hasattr(model, "get_mm_projector"):
-        return model.get_mm_projector(), "mm_projector."
-    return getattr(model.get_model(), "mm_projector", None), "model.mm_projector."
+    """(projector or None, name prefix): under `.model` in LLaVA, at the top level in VILA."""
+    return model.projector()
 
 
 def bind_model(flat, model):

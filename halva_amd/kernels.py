@@ -97,16 +97,27 @@ class _RMSNormFork(torch.autograd.Function):
 _wgrad_ws = {}
 
 
-def wgrad_accumulate(C, A, B, alpha=1.0):
-    """C [M, N] f32 += alpha * A^T B for bf16 column windows A [rows, M], B [rows, N] of wider row-major buffers (LoRA weight
-    gradients, include/halva_hip.h:halva_wgrad_accumulate).  Split over the rows; partials are summed in a fixed order."""
+def _wgrad_workspace(dev):
+    ws = _wgrad_ws.get(dev)
+    if ws is None:
+        ws = _wgrad_ws[dev] = torch.empty(48 * 2 ** 20, dtype=torch.float32, device=dev)      # 192 MB: 30+ slabs at these sizes
+    return ws
+
+
+def _wgrad_operands(C, A, B):
+    """(rows, M, N) of C [M, N] f32 += A^T B after checking the operands: bf16 column windows with unit column stride."""
     rows, M = A.shape
     N = B.shape[1]
     assert B.shape[0] == rows and C.shape == (M, N) and C.dtype == torch.float32 and C.is_contiguous()
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.stride(1) == 1 and B.stride(1) == 1
-    ws = _wgrad_ws.get(C.device)
-    if ws is None:
-        ws = _wgrad_ws[C.device] = torch.empty(48 * 2 ** 20, dtype=torch.float32, device=C.device)      # 192 MB: 30+ slabs at these sizes
+    return rows, M, N
+
+
+def wgrad_accumulate(C, A, B, alpha=1.0):
+    """C [M, N] f32 += alpha * A^T B for bf16 column windows A [rows, M], B [rows, N] of wider row-major buffers (LoRA weight
+    gradients, include/halva_hip.h:halva_wgrad_accumulate).  Split over the rows; partials are summed in a fixed order."""
+    rows, M, N = _wgrad_operands(C, A, B)
+    ws = _wgrad_workspace(C.device)
     call("halva_wgrad_accumulate", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), M, N, rows, float(alpha), ptr(ws), ws.numel(),
          stream_ptr())
 
@@ -114,16 +125,10 @@ def wgrad_accumulate(C, A, B, alpha=1.0):
 def wgrad_accumulate_batch(items):
     """[(C, A, B, alpha), ...] -> every C [M, N] f32 += alpha * A^T B, as ONE launch pair for the two to four products of a LoRA group
     (include/halva_hip.h:halva_wgrad_accumulate_batch); bitwise the results of wgrad_accumulate called once per item."""
-    dev = items[0][0].device
-    ws = _wgrad_ws.get(dev)
-    if ws is None:
-        ws = _wgrad_ws[dev] = torch.empty(48 * 2 ** 20, dtype=torch.float32, device=dev)      # 192 MB: 30+ slabs at these sizes
+    ws = _wgrad_workspace(items[0][0].device)
     arr = (hip.WgradItem * len(items))()
     for it, (C, A, B, alpha) in zip(arr, items):
-        rows, M = A.shape
-        N = B.shape[1]
-        assert B.shape[0] == rows and C.shape == (M, N) and C.dtype == torch.float32 and C.is_contiguous()
-        assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.stride(1) == 1 and B.stride(1) == 1
+        rows, M, N = _wgrad_operands(C, A, B)
         it.A, it.lda, it.B, it.ldb, it.C, it.M, it.N, it.rows, it.alpha = ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), M, N, rows, float(alpha)
     call("halva_wgrad_accumulate_batch", len(items), ctypes.cast(arr, ctypes.c_void_p), ptr(ws), ws.numel(), stream_ptr())
 
@@ -434,57 +439,22 @@ def gemm(A, B, bias=None, trans_a=False, trans_b=False, epilogue=0, out=None, ou
 
 
 class _ProjectorMLP(torch.autograd.Function):
-    """mlp2x_gelu projector (multimodal_projector/builder.py:39-46): Linear -> GELU -> Linear with the bias/GELU
-    epilogue fused into the first GEMM.  The input (CLIP features) carries no gradient (clip_encoder.py:37)."""
+    """Every projector of the two model families as one node: Linear (-> GELU -> Linear)* - `linear` and `mlp<N>x_gelu`
+    (multimodal_projector/builder.py:33-46) - optionally behind DownSampleBlock -> LayerNorm(4c), which makes VILA's mlp_downsample
+    (vila/model/multimodal_projector/base_projector.py:76-83).  Every Linear is one MFMA GEMM with the bias (and, between layers, the
+    GELU) fused into its epilogue.  The input (features of a frozen tower) carries no gradient (clip_encoder.py:37,
+    src_vila/halva_vila_13b.sh:44), so the backward stops at the first Linear - or, with the front, at the LayerNorm parameters.
+    ln_w None: no front.  wb: weight, bias, weight, bias, ..."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2):
-        x2 = _chk(x.reshape(-1, x.shape[-1]).contiguous(), torch.bfloat16, "x")
-        h_pre = torch.empty(x2.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
-        g = gemm(x2, w1, b1, epilogue=1, pre_act=h_pre)
-        y = gemm(g, w2, b2)
-        ctx.save_for_backward(x2, h_pre, g)
-        ctx.params = (w1, b1, w2, b2)
-        return y.view(*x.shape[:-1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, h_pre, g = ctx.saved_tensors
-        w1, b1, w2, b2 = ctx.params
-        dy2 = _chk(dy.reshape(-1, dy.shape[-1]).contiguous(), torch.bfloat16, "dy")
-        M = dy2.shape[0]
-        st = stream_ptr()
-        dw2 = gemm(dy2, g, trans_a=True, trans_b=True, out_dtype=torch.float32)          # dW2[n,k] = sum_m dy[m,n] g[m,k]
-        db2 = torch.zeros(w2.shape[0], dtype=torch.float32, device=dy.device)
-        call("halva_colsum", ptr(dy2), ptr(db2), M, w2.shape[0], st)
-        dg = gemm(dy2, w2, trans_b=True)                                                  # dg[m,k] = sum_n dy[m,n] W2[n,k]
-        dh = torch.empty_like(dg)
-        call("halva_gelu_bwd", ptr(dg), ptr(h_pre), ptr(dh), M, dg.shape[1], st)
-        dw1 = gemm(dh, x2, trans_a=True, trans_b=True, out_dtype=torch.float32)
-        db1 = torch.zeros(w1.shape[0], dtype=torch.float32, device=dy.device)
-        call("halva_colsum", ptr(dh), ptr(db1), M, w1.shape[0], st)
-        grads = []
-        for prm, gr in ((w1, dw1), (b1, db1), (w2, dw2), (b2, db2)):
-            if getattr(prm, "main_grad", None) is not None and getattr(prm, "grad_sink", False):
-                prm.main_grad.add_(gr)             # fp32 accumulation straight into the flat DP/optimizer buffer
-                grads.append(None)
-            else:
-                grads.append(gr.to(prm.dtype))
-        return (None, *grads)
-
-
-def projector_mlp(x, w1, b1, w2, b2):
-    return _ProjectorMLP.apply(x, w1, b1, w2, b2)
-
-
-class _ProjectorChain(torch.autograd.Function):
-    """`linear` and `mlp<N>x_gelu` projectors of any depth (multimodal_projector/builder.py:33-46): Linear (-> GELU -> Linear)*, every
-    Linear one MFMA GEMM with the bias (and, between layers, the GELU) fused into its epilogue.  The input carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, x, *wb):
+    def forward(ctx, x, ln_w, ln_b, eps, *wb):
         ws, bs = wb[0::2], wb[1::2]
-        h = _chk(x.reshape(-1, x.shape[-1]).contiguous(), torch.bfloat16, "x")
+        if ln_w is not None:
+            x = downsample2x2(x.contiguous())
+            ln_in = x.view(-1, x.shape[-1])
+            h, stats = layernorm(ln_in, ln_w, ln_b, eps, want_stats=True)
+        else:
+            h = _chk(x.reshape(-1, x.shape[-1]).contiguous(), torch.bfloat16, "x")
         saved = []
         for i, (w, b) in enumerate(zip(ws, bs)):
             if i + 1 < len(ws):
@@ -495,29 +465,40 @@ class _ProjectorChain(torch.autograd.Function):
                 nxt = gemm(h, w, b)
                 saved.append(h)
             h = nxt
+        if ln_w is not None:
+            saved += [ln_in, stats]
         ctx.save_for_backward(*saved)
-        ctx.params = (ws, bs)
+        ctx.params = (ln_w, ln_b, ws, bs)
         return h.view(*x.shape[:-1], ws[-1].shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        ws, bs = ctx.params
+        ln_w, ln_b, ws, bs = ctx.params
         saved = list(ctx.saved_tensors)
         d = _chk(dy.reshape(-1, dy.shape[-1]).contiguous(), torch.bfloat16, "dy")
         M, st = d.shape[0], stream_ptr()
         pairs = []
         for i in range(len(ws) - 1, -1, -1):
             inp = saved[2 * i]
-            dw = gemm(d, inp, trans_a=True, trans_b=True, out_dtype=torch.float32)
+            dw = gemm(d, inp, trans_a=True, trans_b=True, out_dtype=torch.float32)       # dW[n,k] = sum_m d[m,n] inp[m,k]
             db = torch.zeros(ws[i].shape[0], dtype=torch.float32, device=dy.device)
             call("halva_colsum", ptr(d), ptr(db), M, ws[i].shape[0], st)
             pairs += [(bs[i], db), (ws[i], dw)]
+            if i > 0 or ln_w is not None:         # the first layer's input gradient only feeds halva_layernorm_bwd_params
+                dg = gemm(d, ws[i], trans_b=True)                                         # dg[m,k] = sum_n d[m,n] W[n,k]
             if i > 0:
-                dg = gemm(d, ws[i], trans_b=True)
                 d = torch.empty_like(dg)
                 call("halva_gelu_bwd", ptr(dg), ptr(saved[2 * i - 1]), ptr(d), M, dg.shape[1], st)
-        grads = _sink_or_return(pairs[::-1])
-        return (None, *grads)
+        pairs = pairs[::-1]
+        if ln_w is None:
+            return (None, None, None, None, *_sink_or_return(pairs))
+        ln_in, stats = saved[-2:]
+        c = ln_in.shape[1]
+        dlw = torch.zeros(c, dtype=torch.float32, device=dy.device)
+        dlb = torch.zeros(c, dtype=torch.float32, device=dy.device)
+        call("halva_layernorm_bwd_params", ptr(dg), ptr(ln_in), ptr(stats), ptr(dlw), ptr(dlb), M, c, st)
+        gr = _sink_or_return([(ln_w, dlw), (ln_b, dlb)] + pairs)
+        return (None, gr[0], gr[1], None, *gr[2:])
 
 
 def projector_chain(x, linears):
@@ -525,11 +506,15 @@ def projector_chain(x, linears):
     args = []
     for lin in linears:
         args += [lin.weight, lin.bias]
-    return _ProjectorChain.apply(x, *args)
+    return _ProjectorMLP.apply(x, None, None, None, *args)
+
+
+def projector_mlp(x, w1, b1, w2, b2):
+    return _ProjectorMLP.apply(x, None, None, None, w1, b1, w2, b2)
 
 
 def _sink_or_return(pairs):
-    """Gradient hand-off shared by the projector Functions: fp32 accumulation straight into `.main_grad` (the flat
+    """Gradient hand-off of the projector Function: fp32 accumulation straight into `.main_grad` (the flat
     DP / optimizer buffer) when the parameter is bound to one, else a plain autograd gradient."""
     grads = []
     for prm, gr in pairs:
@@ -565,51 +550,8 @@ def downsample2x2(x):
     return out
 
 
-class _DownsampleMLP(torch.autograd.Function):
-    """mlp_downsample projector (vila/model/multimodal_projector/base_projector.py:76-83): DownSampleBlock ->
-    LayerNorm(4c) -> Linear -> GELU -> Linear.  The input (SigLIP features) carries no gradient (tower frozen,
-    src_vila/halva_vila_13b.sh:44), so the backward stops at the LayerNorm parameters."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, eps, w1, b1, w2, b2):
-        xd = downsample2x2(x.contiguous())
-        x2 = xd.view(-1, xd.shape[-1])
-        xn, stats = layernorm(x2, ln_w, ln_b, eps, want_stats=True)
-        h_pre = torch.empty(x2.shape[0], w1.shape[0], dtype=torch.bfloat16, device=x.device)
-        g = gemm(xn, w1, b1, epilogue=1, pre_act=h_pre)
-        y = gemm(g, w2, b2)
-        ctx.save_for_backward(x2, stats, xn, h_pre, g)
-        ctx.params = (ln_w, ln_b, w1, b1, w2, b2)
-        return y.view(xd.shape[0], xd.shape[1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, stats, xn, h_pre, g = ctx.saved_tensors
-        ln_w, ln_b, w1, b1, w2, b2 = ctx.params
-        dy2 = _chk(dy.reshape(-1, dy.shape[-1]).contiguous(), torch.bfloat16, "dy")
-        M = dy2.shape[0]
-        st = stream_ptr()
-        dev = dy.device
-        dw2 = gemm(dy2, g, trans_a=True, trans_b=True, out_dtype=torch.float32)
-        db2 = torch.zeros(w2.shape[0], dtype=torch.float32, device=dev)
-        call("halva_colsum", ptr(dy2), ptr(db2), M, w2.shape[0], st)
-        dg = gemm(dy2, w2, trans_b=True)
-        dh = torch.empty_like(dg)
-        call("halva_gelu_bwd", ptr(dg), ptr(h_pre), ptr(dh), M, dg.shape[1], st)
-        dw1 = gemm(dh, xn, trans_a=True, trans_b=True, out_dtype=torch.float32)
-        db1 = torch.zeros(w1.shape[0], dtype=torch.float32, device=dev)
-        call("halva_colsum", ptr(dh), ptr(db1), M, w1.shape[0], st)
-        dxn = gemm(dh, w1, trans_b=True)                                                  # [M, 4c]
-        d = x2.shape[1]
-        dlw = torch.zeros(d, dtype=torch.float32, device=dev)
-        dlb = torch.zeros(d, dtype=torch.float32, device=dev)
-        call("halva_layernorm_bwd_params", ptr(dxn), ptr(x2), ptr(stats), ptr(dlw), ptr(dlb), M, d, st)
-        gr = _sink_or_return(((ln_w, dlw), (ln_b, dlb), (w1, dw1), (b1, db1), (w2, dw2), (b2, db2)))
-        return (None, gr[0], gr[1], None, *gr[2:])
-
-
 def downsample_mlp(x, ln_w, ln_b, eps, w1, b1, w2, b2):
-    return _DownsampleMLP.apply(x, ln_w, ln_b, eps, w1, b1, w2, b2)
+    return _ProjectorMLP.apply(x, ln_w, ln_b, eps, w1, b1, w2, b2)
 
 
 def vit_patch_embed(images, weight_kp, bias, patch, d):

@@ -9,18 +9,14 @@ normally never materialised (halva_amd/dpa.py fuses lm_head with the loss kernel
 full fp32 logits for API parity with `LlamaForCausalLM.forward(...).logits.float()` (modelling_llama.py:806).
 """
 import os
-from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import kernels as K
-from . import splice as SP
 from .clip import CLIPVisionTower, _read_checkpoint, build_vision_projector, build_vision_tower
 from .llama import (LlamaConfig, LlamaModel, add_lora, hf_llama_state_dict, load_hf_llama_weights)
-
-IGNORE_INDEX = -100
-IMAGE_TOKEN_INDEX = -200
+from .multimodal import (IGNORE_INDEX, IMAGE_TOKEN_INDEX, CausalLMOutput, FrozenProjectorView, MultimodalMixin,  # noqa: F401
+                         _cpu, random_fill_, reuse_base)
 
 
 class LlavaConfig(LlamaConfig):
@@ -72,12 +68,8 @@ class LlavaLlamaModel(LlavaMetaModel, LlamaModel):
             self.mm_projector = build_vision_projector(config, dtype=dtype, device=device)
 
 
-class CausalLMOutput(SimpleNamespace):
-    pass
-
-
-class LlavaMetaForCausalLM:
-    """reference llava/model/llava_arch.py:71-440"""
+class LlavaMetaForCausalLM(MultimodalMixin):
+    """reference llava/model/llava_arch.py:71-440; the splice, forward tail and generation are halva_amd/multimodal.py's."""
 
     def get_vision_tower(self):
         return self.get_model().get_vision_tower()
@@ -86,48 +78,14 @@ class LlavaMetaForCausalLM:
         feats = self.get_model().get_vision_tower()(images)
         return self.get_model().mm_projector(feats)
 
-    # -- the splice ------------------------------------------------------------------------------
-    def _splice(self, input_ids, attention_mask, labels, signs, images, image_features=None, image_map=None):
-        model = self.get_model()
-        dev = model.embed_tokens.weight.device
+    def _image_features(self, input_ids, attention_mask, images, image_features=None, image_map=None):
+        """Precomputed image_features / image_map are taken as given; a list or 5-D input is concatenated: multi-image samples
+        consume the features in order, one [n_patch, d] block per image token."""
         if image_features is None:
             if type(images) is list or images.ndim == 5:
-                cat = torch.cat([im for im in images], dim=0)
-                image_features = self.encode_images(cat)
-                # multi-image samples: features are consumed in order, one [n_patch, d] block per image token
-            else:
-                image_features = self.encode_images(images)
-        n_patch = image_features.shape[1]
-        plan = SP.plan_splice(_cpu(input_ids), None if attention_mask is None else _cpu(attention_mask),
-                              None if labels is None else _cpu(labels), None if signs is None else _cpu(signs),
-                              n_patch=n_patch, max_len=getattr(self.config, "tokenizer_model_max_length", None),
-                              padding_side=getattr(self.config, "tokenizer_padding_side", "right"), image_map=image_map)
-        embeds = K.splice_rows(model.embed_tokens.weight, image_features.to(torch.bfloat16), plan.src, plan.S, plan.T)
-        return embeds, plan
-
-    def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels, images):
-        vt = self.get_vision_tower()
-        if vt is None or images is None or input_ids.shape[1] == 1:
-            return input_ids, position_ids, attention_mask, past_key_values, None, labels
-        embeds, plan = self._splice(input_ids, attention_mask, labels, None, images)
-        dev = input_ids.device
-        new_labels = None if labels is None else plan.labels.to(dev)
-        new_mask = None if attention_mask is None else plan.mask.to(dev).to(attention_mask.dtype)
-        self._last_plan = plan
-        return None, (None if position_ids is None else position_ids), new_mask, past_key_values, embeds, new_labels
-
-    def prepare_inputs_labels_for_multimodal_signed(self, input_ids, position_ids, attention_mask, past_key_values, labels,
-                                                    images, signs):
-        vt = self.get_vision_tower()
-        if vt is None or images is None or input_ids.shape[1] == 1:
-            return input_ids, position_ids, attention_mask, past_key_values, None, labels, signs
-        embeds, plan = self._splice(input_ids, attention_mask, labels, signs, images)
-        dev = input_ids.device
-        new_labels = None if labels is None else plan.labels.to(dev)
-        new_signs = None if signs is None else plan.signs.to(dev)
-        new_mask = None if attention_mask is None else plan.mask.to(dev).to(attention_mask.dtype)
-        self._last_plan = plan
-        return None, (None if position_ids is None else position_ids), new_mask, past_key_values, embeds, new_labels, new_signs
+                images = torch.cat([im for im in images], dim=0)
+            image_features = self.encode_images(images)
+        return image_features, image_map
 
     def resize_token_embeddings(self, new_num_tokens):
         """HF PreTrainedModel.resize_token_embeddings for this model's two vocabulary-sized tensors: old rows kept, new rows
@@ -185,10 +143,6 @@ class LlavaMetaForCausalLM:
         # (mm_use_im_patch_token alone only touches requires_grad flags that are already False here: llava_arch.py:435-440)
 
 
-def _cpu(t):
-    return t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-
-
 class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
     config_class = LlavaConfig
 
@@ -206,13 +160,17 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
     def get_model(self):
         return self.model
 
-    @property
-    def device(self):
-        return self.lm_head.weight.device
+    def _lm_config(self):
+        return self.config
 
-    @property
-    def dtype(self):
-        return self.lm_head.weight.dtype
+    def _tokens_per_image(self):
+        return self.get_vision_tower().num_patches
+
+    def causal_lm(self):
+        return self, ""
+
+    def projector(self):
+        return getattr(self.model, "mm_projector", None), "model.mm_projector."
 
     def get_input_embeddings(self):
         return self.model.embed_tokens
@@ -248,53 +206,12 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
                 sd["model.mm_projector." + k] = v
         return sd
 
-    # -- forward ---------------------------------------------------------------------------------
-    def hidden_states(self, inputs_embeds, attention_mask=None, seq_start=None, seq_len=None, branch=None, rows=None):
-        """Decoder stack + final norm on inputs_embeds [S, T, d].  The key-padding mask must be one contiguous run per
-        row (what the splice produces); it is the raw [S, T] bool mask of the flash-attn seam
-        (llama_flash_attn_monkey_patch.py:71,98-102)."""
-        S, T, _ = inputs_embeds.shape
-        dev = inputs_embeds.device
-        if seq_len is None:
-            if attention_mask is None:
-                seq_start = torch.zeros(S, dtype=torch.int32)
-                seq_len = torch.full((S,), T, dtype=torch.int32)
-            elif self._last_plan is not None and self._last_plan.mask.shape == attention_mask.shape:
-                seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len     # no device sync
-            else:
-                seq_start, seq_len = SP.spans_from_mask(_cpu(attention_mask))
-        return self.model.run_layers(inputs_embeds.to(torch.bfloat16), seq_start.to(dev), seq_len.to(dev), self._use_lora, branch, rows)
-
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, images=None,
                 return_dict=None):
-        if past_key_values is not None or use_cache:
-            raise NotImplementedError("KV-cache decoding is not part of the DPA training path")
-        if inputs_embeds is None:
-            if images is not None:
-                (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds,
-                 labels) = self.prepare_inputs_labels_for_multimodal(input_ids, position_ids, attention_mask, past_key_values,
-                                                                     labels, images)
-            if inputs_embeds is None:
-                inputs_embeds = self.model.embed_tokens(input_ids)
-        h = self.hidden_states(inputs_embeds, attention_mask)
-        logits = torch.nn.functional.linear(h, self.lm_head.weight).float()
-        loss = None
-        if labels is not None:
-            tgt = labels[..., 1:].contiguous().view(-1)
-            keep = (tgt != IGNORE_INDEX).nonzero().flatten()
-            lg = logits[..., :-1, :].reshape(-1, logits.shape[-1])
-            lp = K.token_logp(lg[keep].contiguous(), tgt[keep].int())
-            loss = -lp.mean()
-        return CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
+        return self._forward_multimodal(input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, labels, use_cache,
+                                        images)[0]
 
-    # -- generation ------------------------------------------------------------------------------
-    def decode_stack(self):
-        """The pieces the KV-cached decode runs on (halva_amd/decode.py)."""
-        from .decode import DecodeStack
-        return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
-
-    @torch.no_grad()
     def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
                  max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, image_sizes=None,
                  **unused):
@@ -303,36 +220,8 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
         input_ids [B, T] (IMAGE_TOKEN_INDEX marks the image; right-padded batches carry attention_mask), images [B, 3, H, W]
         (fp16 accepted).  Returns LongTensor [B, T + n]: the prompt as given, then the new tokens; a row that emitted EOS is padded
         with pad_token_id after it.  Stops when every row is done or after max_new_tokens; one host sync per step."""
-        from . import decode as DEC
-        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
-        if input_ids is None or input_ids.ndim != 2:
-            raise ValueError("generate needs input_ids [B, T]")
-        dev = self.device
-        prompt = input_ids
-        ids = input_ids.to(dev)
-        mask = None if attention_mask is None else attention_mask.to(dev)
-        B, T0 = ids.shape
-        if images is not None:
-            images = [im.to(dev, torch.bfloat16) for im in images] if type(images) is list else images.to(dev, torch.bfloat16)
-        embeds = None
-        if images is not None and self.get_vision_tower() is not None and T0 > 1:
-            self._last_plan = None
-            _, _, new_mask, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, images)
-            plan = self._last_plan
-            seq_start, seq_len = plan.seq_start, plan.seq_len
-        else:
-            if (ids < 0).any():
-                raise ValueError("input_ids hold image tokens but no images (or no vision tower) were given")
-            embeds = self.model.embed_tokens(ids)
-            if mask is None:
-                seq_start, seq_len = torch.zeros(B, dtype=torch.int32), torch.full((B,), T0, dtype=torch.int32)
-            else:
-                seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
-        if int(seq_start.max()) != 0:
-            raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
-        eos_ids, pad = DEC.eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
-        out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt.to(dev))
-        return torch.cat([prompt.to(dev).long(), out], 1)
+        return self._generate_greedy(input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id,
+                                     pad_token_id, stopping_criteria)
 
     __call__ = nn.Module.__call__
 
@@ -351,52 +240,37 @@ def build_random_llava(cfg_kwargs, clip_kwargs, lora_r=0, lora_alpha=0, seed=0, 
     cfg.tokenizer_model_max_length = max_len
     cfg.tokenizer_padding_side = "right"
     g = torch.Generator(device=device).manual_seed(seed)
+    m = LlavaLlamaForCausalLM.__new__(LlavaLlamaForCausalLM)
+    nn.Module.__init__(m)
+    m.config = cfg
+    m.model = LlavaLlamaModel.__new__(LlavaLlamaModel)
+    m.vocab_size = cfg.vocab_size
+    m._last_plan = None
     if share_base_from is None:
-        m = LlavaLlamaForCausalLM.__new__(LlavaLlamaForCausalLM)
-        nn.Module.__init__(m)
-        m.config = cfg
-        m.model = LlavaLlamaModel.__new__(LlavaLlamaModel)
         LlamaModel.__init__(m.model, cfg, torch.bfloat16, device)
         m.model._dtype, m.model._device = torch.bfloat16, device
         m.model.vision_tower = CLIPVisionTower("random-clip", args=cfg, delay_load=True, config=CLIPVisionConfig(**clip_kwargs),
                                                dtype=torch.bfloat16, device=device)
         m.model.vision_tower._alloc()
         m.model.mm_projector = build_vision_projector(cfg, dtype=torch.bfloat16, device=device)
-        m.vocab_size = cfg.vocab_size
         m.lm_head = nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False, dtype=torch.bfloat16, device=device)
-        m._use_lora, m._last_plan = True, None
+        m._use_lora = True
         with torch.no_grad():
-            for n, p in m.named_parameters():
-                if p.ndim >= 2:
-                    p.normal_(0.0, std, generator=g)
-                elif "ln" in n or "norm" in n:
-                    if n.endswith("_b") or n.endswith("bias"):
-                        p.zero_()
-                    else:
-                        p.fill_(1.0)
-                else:
-                    p.normal_(0.0, std, generator=g)
+            random_fill_(m.named_parameters(), g, std)
             vt = m.model.vision_tower
             vt.patch_w[:, 3 * clip_kwargs["patch_size"] ** 2:].zero_()
         m.model.vision_tower.requires_grad_(False)
         m.model.vision_tower.is_loaded = True
     else:
         src = share_base_from
-        m = LlavaLlamaForCausalLM.__new__(LlavaLlamaForCausalLM)
-        nn.Module.__init__(m)
-        m.config = cfg
-        m.model = LlavaLlamaModel.__new__(LlavaLlamaModel)
         LlamaModel.__init__(m.model, LlavaConfig(**dict(cfg_kwargs, num_hidden_layers=0)), torch.bfloat16, device)
         m.model.config = cfg
         m.model._dtype, m.model._device = torch.bfloat16, device
-        m.model.embed_tokens = src.model.embed_tokens
-        m.model.norm = src.model.norm
+        reuse_base(m.model, src.model)
         m.model.vision_tower = src.model.vision_tower
-        m.model.mm_projector = _FrozenProjectorView(src.model.mm_projector)
-        m.model.layers = nn.ModuleList([_BaseOnlyLayer(l) for l in src.model.layers])
-        m.vocab_size = cfg.vocab_size
+        m.model.mm_projector = FrozenProjectorView(src.model.mm_projector)
         m.lm_head = src.lm_head
-        m._use_lora, m._last_plan = False, None
+        m._use_lora = False
     for p in m.parameters():
         p.requires_grad_(False)
     if lora_r:
@@ -404,24 +278,3 @@ def build_random_llava(cfg_kwargs, clip_kwargs, lora_r=0, lora_alpha=0, seed=0, 
         for p in m.model.mm_projector.parameters():
             p.requires_grad_(True)
     return m
-
-
-class _BaseOnlyLayer(nn.Module):
-    """A decoder layer that reuses another layer's frozen base tensors and never applies its LoRA factors."""
-
-    def __init__(self, layer):
-        super().__init__()
-        self._l = [layer]            # not registered: the tensors belong to the policy model
-
-    def forward(self, x, info, use_lora=False, own_x=False, rows=None):
-        return self._l[0](x, info, False, own_x, rows)
-
-
-class _FrozenProjectorView(nn.Module):
-    def __init__(self, proj):
-        super().__init__()
-        self._p = [proj]
-
-    def forward(self, x):
-        with torch.no_grad():
-            return self._p[0](x)

@@ -1,0 +1,215 @@
+"""What the LLaVA wrapper (halva_amd/llava_model.py) and the VILA wrapper (halva_amd/vila_model.py) share: the splice
+contract, the decoder pass over spliced embeddings, the logits / CE tail of `forward`, greedy generation and the
+description the step engine (halva_amd/dpa.py) asks for - each written once, in `MultimodalMixin`.
+
+A wrapper supplies what really differs:
+  get_model()              the Llama stack (embed_tokens / layers / run_layers)
+  lm_head                  the output projection
+  get_vision_tower()       the frozen tower, or None
+  _lm_config()             the config that carries tokenizer_model_max_length / tokenizer_padding_side / eos / pad ids
+  _image_features(...)     images -> (features [n, tokens, d], image_map or None)
+  _tokens_per_image()      image tokens per image after the projector
+  causal_lm(), projector() (module, parameter-name prefix) pairs for the flat trainable buffer
+and the four class attributes below.
+"""
+from types import SimpleNamespace
+
+import torch
+import torch.nn as nn
+
+from . import kernels as K
+from . import splice as SP
+
+IGNORE_INDEX = -100
+IMAGE_TOKEN_INDEX = -200
+_LEFT_PADDED = "generate: left-padded prompts are not supported; pad on the right and pass attention_mask"
+
+
+class CausalLMOutput(SimpleNamespace):
+    pass
+
+
+def _cpu(t):
+    return t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+
+
+class BaseOnlyLayer(nn.Module):
+    """A decoder layer that reuses another layer's frozen base tensors and never applies its LoRA factors."""
+
+    def __init__(self, layer):
+        super().__init__()
+        self._l = [layer]            # not registered: the tensors belong to the policy model
+
+    def forward(self, x, info, use_lora=False, own_x=False, rows=None):
+        return self._l[0](x, info, False, own_x, rows)
+
+
+class FrozenProjectorView(nn.Module):
+    """Another model's projector, run under no_grad; `kind`, `config` and `tokens_per_image` (VILA's MultimodalProjector) are
+    forwarded when the projector has them."""
+
+    def __init__(self, proj):
+        super().__init__()
+        self._p = [proj]             # not registered, see BaseOnlyLayer
+        for a in ("kind", "config", "tokens_per_image"):
+            if hasattr(proj, a):
+                setattr(self, a, getattr(proj, a))
+
+    def forward(self, x, *a, **k):
+        with torch.no_grad():
+            return self._p[0](x)
+
+
+def reuse_base(llama, src_llama):
+    """The reference model == base of the policy: `llama` (built with no layers) takes the policy's frozen tensors."""
+    llama.embed_tokens = src_llama.embed_tokens
+    llama.norm = src_llama.norm
+    llama.layers = nn.ModuleList([BaseOnlyLayer(l) for l in src_llama.layers])
+
+
+def random_fill_(named_params, g, std, is_norm=lambda n: "ln" in n or "norm" in n):
+    """Weights N(0, std) from generator `g` in iteration order, norm weights 1 and norm biases 0 (no draw)."""
+    for n, p in named_params:
+        if p.ndim < 2 and is_norm(n):
+            p.zero_() if (n.endswith("_b") or n.endswith("bias")) else p.fill_(1.0)
+        else:
+            p.normal_(0.0, std, generator=g)
+
+
+class MultimodalMixin:
+    imageless_consumes = True        # an image-less row still advances the running image index (LLaVA; VILA: False)
+    ce_none_without_targets = False  # forward()'s CE on all-ignored labels: mean of an empty tensor (LLaVA) or None (VILA)
+    left_padding_refused_before_splice = False      # generate(): VILA checks the given mask, LLaVA the spans after the splice
+    generate_returns_prompt = True   # generate() -> [prompt | new] (LLaVA) or the new tokens only (VILA)
+
+    @property
+    def device(self):
+        return self.lm_head.weight.device
+
+    @property
+    def dtype(self):
+        return self.lm_head.weight.dtype
+
+    # -- what the step engine needs (halva_amd/dpa.py) -------------------------------------------
+    def dpa_spec(self):
+        """Image tokens per image after the projector, the post-splice truncation length and padding side, and whether an
+        image-less row advances the image index."""
+        lc = self._lm_config()
+        return SimpleNamespace(n_patch=self._tokens_per_image(), max_len=getattr(lc, "tokenizer_model_max_length", None),
+                               padding_side=getattr(lc, "tokenizer_padding_side", "right"),
+                               imageless_consumes=self.imageless_consumes)
+
+    def hidden_states(self, inputs_embeds, attention_mask=None, seq_start=None, seq_len=None, branch=None, rows=None):
+        """Decoder stack + final norm on inputs_embeds [S, T, d].  The key-padding mask must be one contiguous run per
+        row (what the splice produces); it is the raw [S, T] bool mask of the flash-attn seam
+        (llama_flash_attn_monkey_patch.py:71,98-102)."""
+        S, T, _ = inputs_embeds.shape
+        dev = inputs_embeds.device
+        if seq_len is None:
+            if attention_mask is None:
+                seq_start = torch.zeros(S, dtype=torch.int32)
+                seq_len = torch.full((S,), T, dtype=torch.int32)
+            elif self._last_plan is not None and self._last_plan.mask.shape == attention_mask.shape:
+                seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len     # no device sync
+            else:
+                seq_start, seq_len = SP.spans_from_mask(_cpu(attention_mask))
+        return self.get_model().run_layers(inputs_embeds.to(torch.bfloat16), seq_start.to(dev), seq_len.to(dev), self._use_lora,
+                                           branch, rows)
+
+    # -- the splice ------------------------------------------------------------------------------
+    def _splice(self, input_ids, attention_mask, labels, signs, images, **given):
+        """Index plan on the host + one gather launch (halva_amd/splice.py); the plan is kept as `_last_plan`."""
+        feats, image_map = self._image_features(input_ids, attention_mask, images, **given)
+        lc = self._lm_config()
+        plan = SP.plan_splice(_cpu(input_ids), None if attention_mask is None else _cpu(attention_mask),
+                              None if labels is None else _cpu(labels), None if signs is None else _cpu(signs),
+                              n_patch=feats.shape[1], max_len=getattr(lc, "tokenizer_model_max_length", None),
+                              padding_side=getattr(lc, "tokenizer_padding_side", "right"), image_map=image_map,
+                              imageless_consumes=self.imageless_consumes)
+        embeds = K.splice_rows(self.get_model().embed_tokens.weight, feats.to(torch.bfloat16), plan.src, plan.S, plan.T)
+        self._last_plan = plan
+        return embeds, plan
+
+    def prepare_inputs_labels_for_multimodal_signed(self, input_ids, position_ids, attention_mask, past_key_values, labels,
+                                                    images, signs):
+        if self.get_vision_tower() is None or images is None or input_ids.shape[1] == 1:
+            return input_ids, position_ids, attention_mask, past_key_values, None, labels, signs
+        embeds, plan = self._splice(input_ids, attention_mask, labels, signs, images)
+        dev = input_ids.device
+        new_mask = None if attention_mask is None else plan.mask.to(dev).to(attention_mask.dtype)
+        return (None, position_ids, new_mask, past_key_values, embeds, None if labels is None else plan.labels.to(dev),
+                None if signs is None else plan.signs.to(dev))
+
+    def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels, images):
+        return self.prepare_inputs_labels_for_multimodal_signed(input_ids, position_ids, attention_mask, past_key_values, labels,
+                                                                images, None)[:6]
+
+    # -- forward ---------------------------------------------------------------------------------
+    def _forward_multimodal(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, labels, use_cache,
+                            images, signs=None):
+        """The body of `forward`: splice (unless inputs_embeds is given), decoder pass, full fp32 logits and the CE on the kept
+        targets.  Returns (output, labels, signs) with the post-splice labels / signs."""
+        if past_key_values is not None or use_cache:
+            raise NotImplementedError("KV-cache decoding is not part of the DPA training path")
+        if inputs_embeds is None:
+            (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds, labels,
+             signs) = self.prepare_inputs_labels_for_multimodal_signed(input_ids, position_ids, attention_mask, past_key_values,
+                                                                       labels, images, signs)
+            if inputs_embeds is None:
+                inputs_embeds = self.get_model().embed_tokens(input_ids)
+        h = self.hidden_states(inputs_embeds, attention_mask)
+        logits = torch.nn.functional.linear(h, self.lm_head.weight).float()
+        loss = None
+        if labels is not None:
+            tgt = labels[..., 1:].contiguous().view(-1)
+            keep = (tgt != IGNORE_INDEX).nonzero().flatten()
+            if keep.numel() or not self.ce_none_without_targets:
+                lg = logits[..., :-1, :].reshape(-1, logits.shape[-1])
+                loss = -K.token_logp(lg[keep].contiguous(), tgt[keep].int()).mean()
+        out = CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
+        return out, labels, signs
+
+    # -- generation ------------------------------------------------------------------------------
+    def decode_stack(self):
+        """The pieces the KV-cached decode runs on (halva_amd/decode.py): the Llama stack and the head."""
+        from .decode import DecodeStack
+        return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
+
+    @torch.no_grad()
+    def _generate_greedy(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
+                         stopping_criteria):
+        """The body of `generate`: the prompt is spliced when there are images, a tower and more than one token, else embedded;
+        then halva_amd/decode.py:greedy.  Right padding only."""
+        from . import decode as DEC
+        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
+        if input_ids is None or input_ids.ndim != 2:
+            raise ValueError("generate needs input_ids [B, T]")
+        dev = self.device
+        ids = input_ids.to(dev)
+        mask = None if attention_mask is None else attention_mask.to(dev)
+        B, T0 = ids.shape
+        if self.left_padding_refused_before_splice and mask is not None and int(SP.spans_from_mask(_cpu(mask))[0].max()) != 0:
+            raise NotImplementedError(_LEFT_PADDED)            # (the splice would re-pad such rows to the right)
+        embeds = None
+        if images is not None:
+            images = [im.to(dev, torch.bfloat16) for im in images] if type(images) is list else images.to(dev, torch.bfloat16)
+            self._last_plan = None
+            _, _, _, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, images)
+        if embeds is not None:
+            seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len
+        else:
+            if (ids < 0).any():
+                raise ValueError("input_ids hold image tokens but no images (or no vision tower) were given")
+            embeds = self.get_model().embed_tokens(ids)
+            if mask is None:
+                seq_start, seq_len = torch.zeros(B, dtype=torch.int32), torch.full((B,), T0, dtype=torch.int32)
+            else:
+                seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
+        if int(seq_start.max()) != 0:
+            raise NotImplementedError(_LEFT_PADDED)
+        eos_ids, pad = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, dev)
+        if not self.generate_returns_prompt:
+            return DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=None)
+        prompt = input_ids.to(dev)
+        out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt)
+        return torch.cat([prompt.long(), out], 1)

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
-from .clip import CLIPVisionTower, _read_checkpoint
+from .clip import CLIPVisionTower, ViTLayer, run_vit_blocks
 
 
 class SiglipVisionConfig:
@@ -51,17 +51,6 @@ def _pad_head_dim(D):
     raise ValueError("head_dim %d > 128 is not supported by the attention kernel" % D)
 
 
-class _SiglipLayer(nn.Module):
-    def __init__(self, cfg, Dp, dtype, device):
-        super().__init__()
-        d, f, H = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        mk = lambda *s: nn.Parameter(torch.zeros(*s, dtype=dtype, device=device), requires_grad=False)
-        self.ln1_w, self.ln1_b, self.ln2_w, self.ln2_b = mk(d), mk(d), mk(d), mk(d)
-        self.qkv_w, self.qkv_b = mk(3 * H * Dp, d), mk(3 * H * Dp)     # fused [q;k;v], heads padded to Dp lanes
-        self.out_w, self.out_b = mk(d, H * Dp), mk(d)
-        self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b = mk(f, d), mk(f), mk(d, f), mk(d)
-
-
 class SiglipVisionTower(CLIPVisionTower):
     """Same surface as the reference class: forward(images) -> features of hidden_states[select_layer]."""
 
@@ -83,80 +72,42 @@ class SiglipVisionTower(CLIPVisionTower):
         mk = lambda *s: nn.Parameter(torch.zeros(*s, dtype=dtype, device=device), requires_grad=False)
         self.patch_w, self.patch_b = mk(d, self.kp), mk(d)
         self.position_embedding = mk((cfg.image_size // p) ** 2, d)
-        self.layers = nn.ModuleList([_SiglipLayer(cfg, self.head_pad, dtype, device) for _ in range(cfg.num_hidden_layers)])
+        self.layers = nn.ModuleList([ViTLayer(cfg, dtype, device, self.head_pad) for _ in range(cfg.num_hidden_layers)])
 
     def _load_processor(self):
-        try:
-            from transformers import SiglipImageProcessor
-            self.image_processor = SiglipImageProcessor.from_pretrained(self.vision_tower_name)
-        except Exception:
-            self.image_processor = None
-
-    def load_model(self, state_dict=None):
-        if not hasattr(self, "layers"):
-            self._alloc()
-        if state_dict is None and self.vision_tower_name and os.path.isdir(str(self.vision_tower_name)):
-            state_dict = _read_checkpoint(self.vision_tower_name)
-            self._load_processor()
-        if state_dict is not None:
-            self.load_hf_state_dict(state_dict)
-        self.requires_grad_(False)
-        self.is_loaded = True
+        from transformers import SiglipImageProcessor
+        return SiglipImageProcessor.from_pretrained(self.vision_tower_name)
 
     def load_hf_state_dict(self, sd):
         """HF / vendored SiglipVisionModel names, with or without the `vision_model.` prefix.  The pooling head and
         post_layernorm are not on the path (`hidden_states[-2]` is taken before them) and are ignored."""
         sd = {re.sub(r"^(vision_tower\.)*(vision_model\.)*", "", k): v for k, v in sd.items()}
-        cfg = self._cfg
-        d, H, D, Dp = cfg.hidden_size, cfg.num_attention_heads, self.head_dim, self.head_pad
         with torch.no_grad():
             w = sd["embeddings.patch_embedding.weight"]
             self.patch_w.zero_()
             self.patch_w[:, :w[0].numel()].copy_(w.reshape(w.shape[0], -1))
             self.patch_b.copy_(sd["embeddings.patch_embedding.bias"])
             self.position_embedding.copy_(sd["embeddings.position_embedding.weight"])
-            for i, L in enumerate(self.layers):
-                p = "encoder.layers.%d." % i
-                if p + "layer_norm1.weight" not in sd:
-                    continue
-                L.ln1_w.copy_(sd[p + "layer_norm1.weight"]), L.ln1_b.copy_(sd[p + "layer_norm1.bias"])
-                L.ln2_w.copy_(sd[p + "layer_norm2.weight"]), L.ln2_b.copy_(sd[p + "layer_norm2.bias"])
-                L.qkv_w.zero_(), L.qkv_b.zero_(), L.out_w.zero_()
-                for j, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                    wv = L.qkv_w[j * H * Dp:(j + 1) * H * Dp].view(H, Dp, d)
-                    wv[:, :D].copy_(sd[p + "self_attn.%s.weight" % n].view(H, D, d))
-                    bv = L.qkv_b[j * H * Dp:(j + 1) * H * Dp].view(H, Dp)
-                    bv[:, :D].copy_(sd[p + "self_attn.%s.bias" % n].view(H, D))
-                L.out_w.view(d, H, Dp)[:, :, :D].copy_(sd[p + "self_attn.out_proj.weight"].view(d, H, D))
-                L.out_b.copy_(sd[p + "self_attn.out_proj.bias"])
-                L.fc1_w.copy_(sd[p + "mlp.fc1.weight"]), L.fc1_b.copy_(sd[p + "mlp.fc1.bias"])
-                L.fc2_w.copy_(sd[p + "mlp.fc2.weight"]), L.fc2_b.copy_(sd[p + "mlp.fc2.bias"])
+            self._load_layers(sd, self.head_dim)
+
+    @staticmethod
+    def _activation(act):
+        if act == "gelu_pytorch_tanh":
+            return lambda h: F.gelu(h, approximate="tanh")
+        if act == "gelu":
+            return F.gelu
+        if act == "quick_gelu":
+            return lambda h: h * torch.sigmoid(1.702 * h)      # three bf16 tensor ops: rounds differently from K.quick_gelu_
+        raise ValueError("unsupported SigLIP activation %s" % act)
 
     def _features(self, images):
         cfg = self._cfg
         d, H = cfg.hidden_size, cfg.num_attention_heads
         eps = cfg.layer_norm_eps
-        act = cfg.hidden_act
         x = images.to(device=self.device, dtype=self.dtype).contiguous()
         x = K.vit_patch_embed(x, self.patch_w, self.patch_b, cfg.patch_size, d) + self.position_embedding[None]
-        n_run = cfg.num_hidden_layers + 1 + self.select_layer if self.select_layer < 0 else self.select_layer
-        scale = float(self.head_dim) ** -0.5
-        for L in list(self.layers)[:n_run]:
-            h = K.layernorm(x, L.ln1_w, L.ln1_b, eps)
-            qkv = F.linear(h, L.qkv_w, L.qkv_b)
-            a = K.sdpa_full(qkv, H, self.head_pad, scale)
-            x = x + F.linear(a, L.out_w, L.out_b)
-            h = K.layernorm(x, L.ln2_w, L.ln2_b, eps)
-            h = F.linear(h, L.fc1_w, L.fc1_b)
-            if act == "gelu_pytorch_tanh":
-                h = F.gelu(h, approximate="tanh")
-            elif act == "gelu":
-                h = F.gelu(h)
-            elif act == "quick_gelu":
-                h = h * torch.sigmoid(1.702 * h)
-            else:
-                raise ValueError("unsupported SigLIP activation %s" % act)
-            x = x + F.linear(h, L.fc2_w, L.fc2_b)
+        x = run_vit_blocks(x, list(self.layers)[:self._n_run()], H, self.head_pad, float(self.head_dim) ** -0.5, eps,
+                           self._activation(cfg.hidden_act))
         if self.select_feature in ("patch", "cls_patch"):
             # vision_encoder.py:26-29: "patch" drops token 0, "cls_patch" keeps everything.  SigLIP has no class token,
             # so "patch" really drops the first patch - kept bug-for-bug.

@@ -24,10 +24,9 @@ from . import kernels as K
 from . import splice as SP
 from .clip import CLIPVisionConfig, CLIPVisionTower, _read_checkpoint
 from .llama import LlamaConfig, LlamaModel, add_lora, hf_llama_state_dict, load_hf_llama_weights
+from .multimodal import (IGNORE_INDEX, IMAGE_TOKEN_INDEX, CausalLMOutput, FrozenProjectorView, MultimodalMixin,  # noqa: F401
+                         _cpu, random_fill_, reuse_base)
 from .siglip import SiglipVisionConfig, SiglipVisionTower
-
-IGNORE_INDEX = -100
-IMAGE_TOKEN_INDEX = -200
 
 
 class VilaConfig:
@@ -223,18 +222,14 @@ def build_vision_tower(path_or_name, config, dtype=torch.bfloat16, device="cuda"
     return vt
 
 
-class CausalLMOutput(SimpleNamespace):
-    pass
-
-
-def _cpu(t):
-    return t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-
-
 # ------------------------------------------------------------------------------------------------
-class VilaLlavaLlamaModel(nn.Module):
-    """reference class name: vila.model.LlavaLlamaModel."""
+class VilaLlavaLlamaModel(nn.Module, MultimodalMixin):
+    """reference class name: vila.model.LlavaLlamaModel; the splice, forward tail and generation are halva_amd/multimodal.py's."""
     config_class = VilaConfig
+    imageless_consumes = False                                     # vila/model/llava_arch.py:716-718
+    ce_none_without_targets = True
+    left_padding_refused_before_splice = True
+    generate_returns_prompt = False
 
     def __init__(self, config=None, llm=None, vision_tower=None, mm_projector=None, tokenizer=None, model_max_length=None,
                  dtype=torch.bfloat16, device="cuda", **kwargs):
@@ -327,107 +322,41 @@ class VilaLlavaLlamaModel(nn.Module):
     def lm_head(self):
         return self.llm.lm_head
 
-    @property
-    def device(self):
-        return self.llm.lm_head.weight.device
+    def _lm_config(self):
+        return self.llm.config
 
-    @property
-    def dtype(self):
-        return self.llm.lm_head.weight.dtype
+    def _tokens_per_image(self):
+        return self.mm_projector.tokens_per_image(self.vision_tower.num_patches)
 
-    def dpa_spec(self):
-        lc = self.llm.config
-        return SimpleNamespace(n_patch=self.mm_projector.tokens_per_image(self.vision_tower.num_patches),
-                               max_len=getattr(lc, "tokenizer_model_max_length", None),
-                               padding_side=getattr(lc, "tokenizer_padding_side", "right"), imageless_consumes=False)
+    def causal_lm(self):
+        return self.llm, "llm."
 
-    def hidden_states(self, inputs_embeds, attention_mask=None, seq_start=None, seq_len=None, branch=None, rows=None):
-        S, T, _ = inputs_embeds.shape
-        dev = inputs_embeds.device
-        if seq_len is None:
-            if attention_mask is None:
-                seq_start = torch.zeros(S, dtype=torch.int32)
-                seq_len = torch.full((S,), T, dtype=torch.int32)
-            elif self._last_plan is not None and self._last_plan.mask.shape == attention_mask.shape:
-                seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len
-            else:
-                seq_start, seq_len = SP.spans_from_mask(_cpu(attention_mask))
-        return self.llm.model.run_layers(inputs_embeds.to(torch.bfloat16), seq_start.to(dev), seq_len.to(dev), self._use_lora, branch, rows)
+    def projector(self):
+        return self.mm_projector, "mm_projector."
 
-    # -- the splice (llava_arch.py:264-871) -------------------------------------------------------
-    def _splice(self, input_ids, attention_mask, labels, signs, images):
+    def _image_features(self, input_ids, attention_mask, images):
+        """llava_arch.py:650-653: [B, n, 3, H, W] or a list is flattened; a row consumes one image per image token, and asking for
+        more images than were given is the reference's IndexError."""
         if type(images) is list:
             images = torch.cat([im if im.ndim == 4 else im[None] for im in images], dim=0)
         elif images.ndim == 5:
             images = images.flatten(0, 1)
         feats = self.encode_images(images)
-        sp = self.dpa_spec()
         _, used = SP.image_slots(_cpu(input_ids), None if attention_mask is None else _cpu(attention_mask), False)
         if used > feats.shape[0]:
             raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (feats.shape[0], feats.shape[0]))
-        plan = SP.plan_splice(_cpu(input_ids), None if attention_mask is None else _cpu(attention_mask),
-                              None if labels is None else _cpu(labels), None if signs is None else _cpu(signs),
-                              n_patch=feats.shape[1], max_len=sp.max_len, padding_side=sp.padding_side,
-                              imageless_consumes=False)
-        w = self.llm.model.embed_tokens.weight
-        embeds = K.splice_rows(w, feats.to(torch.bfloat16), plan.src, plan.S, plan.T)
-        self._last_plan = plan
-        return embeds, plan
-
-    def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels, images):
-        if self.vision_tower is None or images is None or input_ids.shape[1] == 1:
-            return input_ids, position_ids, attention_mask, past_key_values, None, labels
-        embeds, plan = self._splice(input_ids, attention_mask, labels, None, images)
-        dev = input_ids.device
-        new_mask = None if attention_mask is None else plan.mask.to(dev).to(attention_mask.dtype)
-        return (None, position_ids, new_mask, past_key_values, embeds, None if labels is None else plan.labels.to(dev))
-
-    def prepare_inputs_labels_for_multimodal_signed(self, input_ids, position_ids, attention_mask, past_key_values, labels,
-                                                    images, signs):
-        if self.vision_tower is None or images is None or input_ids.shape[1] == 1:
-            return input_ids, position_ids, attention_mask, past_key_values, None, labels, signs
-        embeds, plan = self._splice(input_ids, attention_mask, labels, signs, images)
-        dev = input_ids.device
-        new_mask = None if attention_mask is None else plan.mask.to(dev).to(attention_mask.dtype)
-        return (None, position_ids, new_mask, past_key_values, embeds, None if labels is None else plan.labels.to(dev),
-                None if signs is None else plan.signs.to(dev))
+        return feats, None
 
     # -- forward (llava_llama.py:83-177) ----------------------------------------------------------
     def forward(self, input_ids=None, images=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, labels=None, use_cache=None, output_attentions=None, output_hidden_states=None,
                 return_dict=None, signs=None):
-        if past_key_values is not None or use_cache:
-            raise NotImplementedError("KV-cache decoding is not part of the DPA training path")
-        if inputs_embeds is None:
-            if signs is not None:
-                (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds, labels,
-                 signs) = self.prepare_inputs_labels_for_multimodal_signed(input_ids, position_ids, attention_mask,
-                                                                           past_key_values, labels, images, signs)
-            else:
-                (input_ids, position_ids, attention_mask, past_key_values, inputs_embeds,
-                 labels) = self.prepare_inputs_labels_for_multimodal(input_ids, position_ids, attention_mask, past_key_values,
-                                                                     labels, images)
-            if inputs_embeds is None:
-                inputs_embeds = self.llm.model.embed_tokens(input_ids)
-        h = self.hidden_states(inputs_embeds, attention_mask)
-        logits = torch.nn.functional.linear(h, self.llm.lm_head.weight).float()
-        loss = None
-        if labels is not None:                                     # the CE the reference computes and never uses
-            tgt = labels[..., 1:].contiguous().view(-1)
-            keep = (tgt != IGNORE_INDEX).nonzero().flatten()
-            if keep.numel():
-                lg = logits[..., :-1, :].reshape(-1, logits.shape[-1])
-                loss = -K.token_logp(lg[keep].contiguous(), tgt[keep].int()).mean()
-        return CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None,
-                              labels=labels, signs=signs)
+        out, labels, signs = self._forward_multimodal(input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, labels,
+                                                      use_cache, images, signs)
+        out.labels, out.signs = labels, signs
+        return out
 
     # -- generation (llava_llama.py:180-206) ------------------------------------------------------
-    def decode_stack(self):
-        """The pieces the KV-cached decode runs on (halva_amd/decode.py): the `.llm`'s Llama stack and head."""
-        from .decode import DecodeStack
-        return DecodeStack(self.llm.model, self.llm.lm_head.weight, self._use_lora)
-
-    @torch.no_grad()
     def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
                  max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, **unused):
         """Greedy decoding with a KV cache: the call of the reference's VILA hallucination benchmarks (eval_hall_vila/*: do_sample=False,
@@ -441,36 +370,8 @@ class VilaLlavaLlamaModel(nn.Module):
         returns [B, T + n] instead.  A row that emitted EOS is padded with pad_token_id after it; the loop stops when every row is done
         or after max_new_tokens.  stopping_criteria (a callable or a list of them; any True stops the batch) see the new tokens only,
         as HF hands them over for inputs_embeds generation."""
-        from . import decode as DEC
-        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
-        if input_ids is None or input_ids.ndim != 2:
-            raise ValueError("generate needs input_ids [B, T]")
-        dev = self.device
-        ids = input_ids.to(dev)
-        mask = None if attention_mask is None else attention_mask.to(dev)
-        B, T0 = ids.shape
-        if mask is not None and int(SP.spans_from_mask(_cpu(mask))[0].max()) != 0:
-            # (the splice would re-pad such rows to the right; the contract is the LLaVA one: right padding only)
-            raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
-        embeds = None
-        if images is not None:
-            images = [im.to(dev, torch.bfloat16) for im in images] if type(images) is list else images.to(dev, torch.bfloat16)
-            self._last_plan = None
-            _, _, _, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, images)
-        if embeds is not None:
-            seq_start, seq_len = self._last_plan.seq_start, self._last_plan.seq_len
-        else:
-            if (ids < 0).any():
-                raise ValueError("input_ids hold image tokens but no images (or no vision tower) were given")
-            embeds = self.llm.model.embed_tokens(ids)
-            if mask is None:
-                seq_start, seq_len = torch.zeros(B, dtype=torch.int32), torch.full((B,), T0, dtype=torch.int32)
-            else:
-                seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
-        if int(seq_start.max()) != 0:
-            raise NotImplementedError("generate: left-padded prompts are not supported; pad on the right and pass attention_mask")
-        eos_ids, pad = DEC.eos_and_pad(self.llm.config, eos_token_id, pad_token_id, dev)
-        return DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=None)
+        return self._generate_greedy(input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id,
+                                     pad_token_id, stopping_criteria)
 
 
 def _load_tokenizer(llm_path, model_max_length):
@@ -481,30 +382,6 @@ def _load_tokenizer(llm_path, model_max_length):
                                              legacy=False)
     except Exception:
         return None
-
-
-# ------------------------------------------------------------------------------------------------
-class _BaseOnlyLayer(nn.Module):
-    def __init__(self, layer):
-        super().__init__()
-        self._l = [layer]
-
-    def forward(self, x, info, use_lora=False, own_x=False, rows=None):
-        return self._l[0](x, info, False, own_x, rows)
-
-
-class _FrozenProjectorView(nn.Module):
-    def __init__(self, proj):
-        super().__init__()
-        self._p = [proj]
-        self.kind, self.config = proj.kind, proj.config
-
-    def tokens_per_image(self, n):
-        return self._p[0].tokens_per_image(n)
-
-    def forward(self, x, *a, **k):
-        with torch.no_grad():
-            return self._p[0](x)
 
 
 def build_random_vila(llm_kwargs, vision_kwargs, projector="mlp_downsample", tower="siglip", lora_r=0, lora_alpha=0, seed=0,
@@ -529,13 +406,9 @@ def build_random_vila(llm_kwargs, vision_kwargs, projector="mlp_downsample", tow
         proj = MultimodalProjector(projector, cfg, dtype=dtype, device=device)
         with torch.no_grad():
             for mod in (llm, vt, proj):
-                for n, p in mod.named_parameters():
-                    if p.ndim >= 2:
-                        p.normal_(0.0, std, generator=g)
-                    elif "ln" in n or "norm" in n or (mod is proj and n.startswith("layers.1.") and projector == "mlp_downsample"):
-                        p.zero_() if (n.endswith("_b") or n.endswith("bias")) else p.fill_(1.0)
-                    else:
-                        p.normal_(0.0, std, generator=g)
+                ln_of_proj = mod is proj and projector == "mlp_downsample"
+                random_fill_(mod.named_parameters(), g, std,
+                             lambda n: "ln" in n or "norm" in n or (ln_of_proj and n.startswith("layers.1.")))
             vt.patch_w[:, 3 * vision_kwargs["patch_size"] ** 2:].zero_()
             if tower == "siglip" and vt.head_pad != vt.head_dim:                     # keep the pad lanes exactly zero
                 H, D, Dp, d = vt._cfg.num_attention_heads, vt.head_dim, vt.head_pad, vt._cfg.hidden_size
@@ -554,13 +427,11 @@ def build_random_vila(llm_kwargs, vision_kwargs, projector="mlp_downsample", tow
         llm.config = src.llm.config
         llm.model = LlamaModel(lc, dtype, device)
         llm.model.config = src.llm.config
-        llm.model.embed_tokens = src.llm.model.embed_tokens
-        llm.model.norm = src.llm.model.norm
-        llm.model.layers = nn.ModuleList([_BaseOnlyLayer(l) for l in src.llm.model.layers])
+        reuse_base(llm.model, src.llm.model)
         llm.vocab_size = src.llm.vocab_size
         llm.lm_head = src.llm.lm_head
         llm.pad_token_id = None
-        m = VilaLlavaLlamaModel(cfg, llm=llm, vision_tower=src.vision_tower, mm_projector=_FrozenProjectorView(src.mm_projector),
+        m = VilaLlavaLlamaModel(cfg, llm=llm, vision_tower=src.vision_tower, mm_projector=FrozenProjectorView(src.mm_projector),
                                 dtype=dtype, device=device)
         m._use_lora = False
     m.llm.config.tokenizer_model_max_length = max_len

@@ -582,6 +582,72 @@ def test_projector_fwd_bwd():
         assert rel_err(dev[k_].grad, Wf[k_].grad) < 1.5e-2, k_
 
 
+def _projector_against_float_torch(proj, reference, x, sink, tol_y, tol_g):
+    """Output and every parameter gradient of `proj` on x against `reference(x, {name: float parameter})`, the same bf16 values run in
+    float torch; sink=True: the fp32 sums land in `.main_grad` and autograd returns None."""
+    g = torch.Generator().manual_seed(61)
+    W = {n: bf(torch.randn(p.shape, generator=g) * 0.1 + (1.0 if "layers.1.weight" in n else 0.0)) for n, p in proj.named_parameters()}
+    proj.load_state_dict(W)
+    for p in proj.parameters():
+        p.requires_grad_(True)
+        if sink:
+            p.main_grad, p.grad_sink = torch.zeros(p.shape, dtype=torch.float32, device=DEV), True
+    y = proj(x.to(DEV))
+    dy = bf(torch.randn(y.shape, generator=g))
+    y.backward(dy.to(DEV))
+    Wf = {n: v.float().requires_grad_(True) for n, v in W.items()}
+    ref = reference(x.float(), Wf)
+    ref.backward(dy.float())
+    print("output rel_err %.3e" % rel_err(y, ref))
+    assert y.shape == ref.shape and rel_err(y, ref) < tol_y
+    for n, p in proj.named_parameters():
+        assert (p.grad is None) == sink, n
+        got = p.main_grad if sink else p.grad
+        print("%s rel_err %.3e" % (n, rel_err(got, Wf[n].grad)))
+        assert rel_err(got, Wf[n].grad) < tol_g, n
+
+
+@pytest.mark.parametrize("sink", [False, True], ids=["autograd", "main_grad"])
+@pytest.mark.parametrize("kind", ["linear", "mlp3x_gelu"])
+def test_projector_types_beside_the_shipped_one(kind, sink):
+    """`linear` and `mlp3x_gelu` through build_vision_projector, [2, 9, 64] -> 128: 18 rows, no multiple of 8 (as 196 rows per image
+    is none; halva_gemm_bf16 asks a multiple of 8 of the contiguous dimensions only, which 64 and 128 are).  Bounds of
+    test_projector_fwd_bwd."""
+    from types import SimpleNamespace
+    from halva_amd.clip import build_vision_projector
+    proj = build_vision_projector(SimpleNamespace(mm_projector_type=kind, mm_hidden_size=64, hidden_size=128), device=DEV)
+    x = bf(torch.randn(2, 9, 64, generator=torch.Generator().manual_seed(60)))
+
+    def reference(h, W):
+        if kind == "linear":
+            return F.linear(h, W["weight"], W["bias"])
+        for i in (0, 2, 4):
+            h = F.linear(h, W["%d.weight" % i], W["%d.bias" % i])
+            h = F.gelu(h) if i < 4 else h
+        return h
+    _projector_against_float_torch(proj, reference, x, sink, 8e-3, 1.5e-2)
+
+
+@pytest.mark.parametrize("sink", [False, True], ids=["autograd", "main_grad"])
+def test_mlp_downsample_on_an_odd_grid(sink):
+    """[2, 9, 32]: g = 3, zero padded to a 2 x 2 grid of 4c = 128 channels (out[n, b*G + a, (f*2 + e)*c + ch] = x[n, (2a + f)*g + 2b + e, ch],
+    halva_amd/csrc/vision.hip) -> LayerNorm -> Linear -> GELU -> Linear.  Tolerances of tests/test_vila_gpu.py for the same Function."""
+    from types import SimpleNamespace
+    from halva_amd.vila_model import MultimodalProjector
+    proj = MultimodalProjector("mlp_downsample", SimpleNamespace(mm_hidden_size=32, hidden_size=128), device=DEV)
+    x = bf(torch.randn(2, 9, 32, generator=torch.Generator().manual_seed(62)))
+
+    def reference(h, W):
+        n, c = h.shape[0], h.shape[2]
+        hp = h.new_zeros(n, 4, 4, c)
+        hp[:, :3, :3] = h.view(n, 3, 3, c)
+        h = hp.view(n, 2, 2, 2, 2, c).permute(0, 3, 1, 2, 4, 5).reshape(n, 4, 4 * c)            # [n, a, f, b, e, c] -> [n, b, a, f, e, c]
+        h = F.layer_norm(h, (4 * c,), W["layers.1.weight"], W["layers.1.bias"], proj.layers[1].eps)
+        h = F.gelu(F.linear(h, W["layers.2.weight"], W["layers.2.bias"]))
+        return F.linear(h, W["layers.4.weight"], W["layers.4.bias"])
+    _projector_against_float_torch(proj, reference, x, sink, 2e-2, 3e-2)
+
+
 def test_clip_patch_embed():
     n, hw, p, d = 3, 336, 14, 256
     g = torch.Generator().manual_seed(7)
