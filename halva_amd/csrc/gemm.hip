@@ -390,6 +390,102 @@ __global__ __launch_bounds__(256) void splitk_reduce_batch_kernel(const WgradBat
     *c = *c + s * b.alpha[q];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// halva_lora_merge: w[n, k] <- bf16( w[n, k] + scale * sum_j B[n, j] A[j, k] ) in place on a strided window of a fused weight - a load-time
+// pass whose whole cost is reading and writing w once, so: no LDS, no pipeline, one plain tile per wave.
+// Workgroup = 4 waves over a [32 n x 256 k] tile, wave w the 64 columns from 64 w on, as two 32x32x16 MFMA tiles.  The MFMA's row index is the
+// k of w and its column index the n, with rows PERMUTED so that the 16 accumulator registers of a lane are 16 CONSECUTIVE k of one weight row:
+// MFMA row i = 8 q + 4 h + e (q = i >> 3, h = (i >> 2) & 1, e = i & 3) stands for column 16 h + 4 q + e of the tile, so lane (n = lane & 31,
+// h = lane >> 5) holds columns 16 h + (4 q + e) = 16 h + reg in acc[reg]: two 16-byte loads and two 16-byte stores of w per lane and tile.
+// The A fragment (LoRA A^T: k on the row, j contracted) is gathered element by element from [r, K] (one j per load; A is at most r x K, L2-resident),
+// the B fragment is one 16-byte load of B[n, 8 h' ..] where the factor's rows allow it.  j runs in steps of 16 in ascending order, zero-filled past r:
+// one fixed summation order, no split, no atomics - the same bits on every run.
+struct MergeParams {
+    bf16_t* w;
+    const bf16_t* B;
+    const bf16_t* A;
+    int64_t ldw, ldb, lda;
+    int N, K, r;
+    float scale;
+    int w_vec, b_vec;      // 16-byte accesses allowed on w / B (base pointer and row stride aligned)
+};
+
+__device__ __forceinline__ bf16_t merge_one(bf16_t w, float acc, float scale) {
+    const float u = scale * acc;
+    return u == 0.f ? w : f32_to_bf16(bf16_to_f32(w) + u);      // (a zero update keeps the weight's own bits, -0 and NaN payloads included)
+}
+
+__global__ __launch_bounds__(256) void lora_merge_kernel(const MergeParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
+    const int n = blockIdx.y * 32 + c;
+    const int kw = blockIdx.x * 256 + wave * 64;      // this wave's first column
+    if (kw >= p.K) return;
+    const bool n_ok = n < p.N;
+    // the column of w that MFMA row (lane & 31) of tile t stands for: kw + 32 t + krow
+    const int krow = 16 * ((c >> 2) & 1) + 4 * (c >> 3) + (c & 3);
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    const bf16_t* brow = p.B + (int64_t)n * p.ldb;
+    for (int j0 = 0; j0 < p.r; j0 += 16) {
+        const int jl = j0 + 8 * h;      // this lane's 8 values of j
+        s16x8 bfrag = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (n_ok) {
+            if (p.b_vec && jl + 8 <= p.r) {
+                bfrag = *reinterpret_cast<const s16x8*>(brow + jl);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (jl + e < p.r) bfrag[e] = (short)brow[jl + e];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int k = kw + 32 * t + krow;
+            s16x8 afrag = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (k < p.K) {
+                const bf16_t* acol = p.A + (int64_t)jl * p.lda + k;
+                if (jl + 8 <= p.r) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) afrag[e] = (short)acol[(int64_t)e * p.lda];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (jl + e < p.r) afrag[e] = (short)acol[(int64_t)e * p.lda];
+                }
+            }
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag), __builtin_bit_cast(bf16x8, bfrag), acc[t], 0, 0, 0);
+        }
+    }
+    if (!n_ok) return;
+    bf16_t* wrow = p.w + (int64_t)n * p.ldw;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int k0 = kw + 32 * t + 16 * h;      // acc[t][i] <-> column k0 + i
+        if (k0 >= p.K) continue;
+        if (p.w_vec && k0 + 16 <= p.K) {
+            u32x4* wp = reinterpret_cast<u32x4*>(wrow + k0);
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+                u32x4 x = wp[v];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const unsigned lo = merge_one((bf16_t)(x[d] & 0xffffu), acc[t][8 * v + 2 * d], p.scale);
+                    const unsigned hi = merge_one((bf16_t)(x[d] >> 16), acc[t][8 * v + 2 * d + 1], p.scale);
+                    x[d] = lo | (hi << 16);
+                }
+                wp[v] = x;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (k0 + i < p.K) wrow[k0 + i] = merge_one(wrow[k0 + i], acc[t][i], p.scale);
+        }
+    }
+}
+
 template <bool TA, bool TB>
 int launch_gemm(const GemmParams& p, hipStream_t st) {
     const dim3 grid((p.N + 127) / 128, (p.M + 127) / 128, p.ksplit > 0 ? (p.K + p.ksplit - 1) / p.ksplit : 1), block(256);
@@ -618,6 +714,27 @@ extern "C" int halva_transpose_bf16(const void* src, int64_t ld_src, void* dst, 
     hipLaunchKernelGGL(transpose_bf16_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, ld_src,
                        (bf16_t*)dst, ld_dst, rows, cols);
     HALVA_CHECK_LAUNCH("transpose_bf16");
+    return HALVA_OK;
+}
+
+extern "C" int halva_lora_merge(void* w, int64_t ldw, const void* B, int64_t ldb, const void* A, int64_t lda, int N, int K, int r, float scale,
+                                void* stream) {
+    HALVA_CHECK_ARG(w && B && A, "lora_merge: null pointer");
+    HALVA_CHECK_ARG(N > 0 && K > 0, "lora_merge: bad sizes N=%d K=%d", N, K);
+    HALVA_CHECK_ARG(r >= 1, "lora_merge: rank r=%d must be at least 1", r);
+    HALVA_CHECK_ARG(ldw >= K && lda >= K && ldb >= r, "lora_merge: row strides ldw=%lld lda=%lld ldb=%lld must cover K=%d, K and r=%d columns",
+                    (long long)ldw, (long long)lda, (long long)ldb, K, r);
+    MergeParams p{};
+    p.w = (bf16_t*)w;
+    p.B = (const bf16_t*)B;
+    p.A = (const bf16_t*)A;
+    p.ldw = ldw, p.ldb = ldb, p.lda = lda;
+    p.N = N, p.K = K, p.r = r;
+    p.scale = scale;
+    p.w_vec = ((uintptr_t)w % 16 == 0) && ldw % 8 == 0;
+    p.b_vec = ((uintptr_t)B % 16 == 0) && ldb % 8 == 0;
+    hipLaunchKernelGGL(lora_merge_kernel, dim3((K + 255) / 256, (N + 31) / 32), dim3(256), 0, (hipStream_t)stream, p);
+    HALVA_CHECK_LAUNCH("lora_merge");
     return HALVA_OK;
 }
 

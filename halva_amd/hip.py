@@ -50,6 +50,7 @@ SIGNATURES = {
     "halva_colsum": [_P, _P, _L, _I, _P],
     "halva_quick_gelu": [_P, _P, _L, _P],
     "halva_transpose_bf16": [_P, _L, _P, _L, _I, _I, _P],
+    "halva_lora_merge": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _F, _P],
     "halva_splice_rows": [_P, _P, _P, _P, _L, _I, _P],
     "halva_token_logp_fwd": [_P, _I, _L, _P, _P, _P, _L, _I, _P],
     "halva_token_logp_bwd": [_P, _I, _L, _P, _P, _P, _P, _L, _I, _P],

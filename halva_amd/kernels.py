@@ -679,6 +679,18 @@ def transpose_into(dst, src):
     return dst
 
 
+def lora_merge(w, B, A, scale):
+    """w [N, K] <- bf16(w + scale * B A) in place: w a bf16 window (unit column stride, any row stride) of a fused weight, B [N, r] and
+    A [r, K] the target's LoRA factors (include/halva_hip.h:halva_lora_merge).  fp32 accumulation in a fixed order, one rounding."""
+    N, Kw = w.shape
+    r = A.shape[0]
+    assert B.shape == (N, r) and A.shape == (r, Kw), (w.shape, B.shape, A.shape)
+    for t in (w, B, A):
+        assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+    call("halva_lora_merge", ptr(w), w.stride(0), ptr(B), B.stride(0), ptr(A), A.stride(0), N, Kw, r, float(scale), stream_ptr())
+    return w
+
+
 def probe_layouts(device="cuda"):
     out = torch.zeros(256 + 1024, dtype=torch.int32, device=device)
     call("halva_probe_layouts", ptr(out), out.numel(), stream_ptr())

@@ -316,6 +316,33 @@ class LoraGroup(nn.Module):
                 self.weight_cat_t[:K].addmm_(self.A_cat.data.t(), self.weight_cat_t[K:K + G * r])
         self._tail_versions = tuple(B._version for B in self._Bs()) + (self.A_cat._version,)
 
+    def merge_(self):
+        """peft's merge_and_unload for this group, for inference and export: each target's rows of the base weight become
+        bf16(W + scale * B A) (halva_lora_merge: fp32 accumulation in a fixed order, one rounding - the bits do not depend on the
+        library GEMM tables), then the factors, the tail columns and the dgrad copy are dropped and the group is back in the LoRA-free
+        layout of __init__.  Lossy (one bf16 rounding of W) and one-way; a group without factors is left alone.  -> merged anything."""
+        if self.A_cat is None:
+            return False
+        if self.grad_sink:
+            raise RuntimeError("merge_: this group's gradient sink is set - a trainer has bound the model; merging is for inference")
+        K, r = self.in_features, self.r
+        with torch.no_grad():
+            off = 0
+            for g, (B, n) in enumerate(zip(self._Bs(), self.outs)):
+                K_.lora_merge(self.weight_cat.data[off:off + n, :K], B.data, self.A_cat.data[g * r:(g + 1) * r], self.scale)
+                off += n
+            pad = 64 if K % 1024 == 0 else 0
+            wc = torch.zeros(self.weight_cat.shape[0], K + pad, dtype=self.weight_cat.dtype, device=self.weight_cat.device)
+            wc[:, :K].copy_(self.weight_cat.data[:, :K])
+        self.weight_cat = nn.Parameter(wc, requires_grad=False)
+        for t in self.targets():
+            del t.lora_B["default"]
+        self.A_cat = None
+        self.weight_cat_t = None
+        self._tail_versions = None
+        self.scale, self.r = 0.0, 0
+        return True
+
     def lora_state(self):
         """{peft-style name: tensor} for this group's targets."""
         out = {}
@@ -443,6 +470,17 @@ class LlamaModel(nn.Module):
         self.gradient_checkpointing = False
         self.grad_ready_hook = None     # callable(layer index): set for ONE forward by DPAEngine; fired from that forward's
         self._rope = {}                 # backward when the gradient of a layer's input exists (halva_amd/dp.py:GradReducer)
+
+    def merge_and_unload(self):
+        """Merge every LoRA group into its base weight (LoraGroup.merge_) and drop the factors; a model without factors - never
+        attached, or merged before - is left as it is.  Refused once a trainer has set the gradient sink.  Returns self."""
+        groups = [grp for layer in self.layers if hasattr(layer, "groups") for _, grp in layer.groups()]
+        if any(grp.grad_sink for grp in groups):
+            raise RuntimeError("merge_and_unload: the gradient sink of this model is set (a trainer has bound it); merging is lossy and "
+                               "meant for inference and export")
+        for grp in groups:
+            grp.merge_()
+        return self
 
     def rope(self, T, device):
         key = (str(device), max(T, 1))

@@ -206,6 +206,19 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
                 sd["model.mm_projector." + k] = v
         return sd
 
+    def save_pretrained(self, path, state_dict=None):
+        """Write a full checkpoint directory that from_pretrained loads: config.json + model.safetensors with the standard HF Llama
+        names (the fused qkv / gate_up rows split back per projection) and the projector under `model.mm_projector.*`.  A model
+        that still carries LoRA factors is refused - they would be dropped silently; merge_and_unload() first."""
+        from safetensors.torch import save_file
+        if state_dict is None and any(grp.A_cat is not None for layer in self.model.layers for _, grp in layer.groups()):
+            raise RuntimeError("save_pretrained writes a LoRA-free checkpoint: call merge_and_unload() first (the adapter itself is "
+                               "written by llava/train/train_halva.py:save_lora_outputs)")
+        os.makedirs(path, exist_ok=True)
+        self.config.save_pretrained(path)
+        sd = self.hf_state_dict() if state_dict is None else state_dict
+        save_file({k: v.detach().cpu().contiguous() for k, v in sd.items()}, os.path.join(path, "model.safetensors"))
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, images=None,
                 return_dict=None):

@@ -169,6 +169,15 @@ class MultimodalMixin:
         out = CausalLMOutput(loss=loss, logits=logits, past_key_values=None, hidden_states=None, attentions=None)
         return out, labels, signs
 
+    # -- inference / export ----------------------------------------------------------------------
+    def merge_and_unload(self):
+        """peft's merge_and_unload, as the reference's loaders call it before evaluation: every LoRA group of the Llama stack is
+        folded into its base weight (halva_amd/llama.py:LlamaModel.merge_and_unload) and the model runs LoRA-free from then on.
+        A second call is a no-op; a model a trainer has bound (gradient sink set) is refused.  Returns self."""
+        self.get_model().merge_and_unload()
+        self._use_lora = False
+        return self
+
     # -- generation ------------------------------------------------------------------------------
     def decode_stack(self):
         """The pieces the KV-cached decode runs on (halva_amd/decode.py): the Llama stack and the head."""

@@ -208,6 +208,15 @@ int halva_colsum(const void* x, float* out, int64_t M, int N, void* stream);
  * (halva_amd/llama.py:LoraGroup.refresh_tail; the reference has no counterpart - peft keeps W, A, B apart and autograd forms dx from each):
  * `torch.addmm(W.t(), ...)` spent 0.45 ms per group copying the strided W^T with the framework's element-wise copy kernel. */
 int halva_transpose_bf16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int rows, int cols, void* stream);
+/* Merge one LoRA target into its base weight, in place (peft's merge_and_unload, which the reference's loaders call before evaluation:
+ * llava/model/builder.py:70-71, vila/model/builder_halva.py:137-138):
+ *   w[n, k] <- bf16_rne( float(w[n, k]) + scale * sum_{j < r} float(B[n, j]) * float(A[j, k]) ),   n < N, k < K
+ * w [N, K] is a window of a wider row-major bf16 buffer (row stride ldw >= K elements: rows [off, off + n) and columns [0, in) of a fused
+ * weight); B [N, r] and A [r, K] bf16 with row strides ldb, lda.  fp32 accumulation on the MFMA in ascending j (one fixed order: no split
+ * over j, no atomics - the same bits on every run, whatever GEMM tables the framework uses), one rounding, every element of w read and
+ * written once; nothing outside the window is read or written.  Any N, K, r >= 1; 16-byte accesses where pointer and stride allow. */
+int halva_lora_merge(void* w, int64_t ldw, const void* B, int64_t ldb, const void* A, int64_t lda, int N, int K, int r, float scale,
+                     void* stream);
 
 /* ---- vision-side row kernels (VILA path).
  * LayerNorm over rows of [rows, d] bf16 (d % 8 == 0, d <= 8192): the nn.LayerNorm of mlp_downsample

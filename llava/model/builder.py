@@ -3,7 +3,9 @@
   * LoRA (`lora` in model_name, model_base given): model_base is an HF LLaVA directory; model_path holds adapter_model.bin,
     non_lora_trainables.bin, adapter_config.json and config.json as llava/train/train_halva.py:save_lora_outputs writes them.  The
     PEFT-named factors go back onto the LoraGroup factors (the inverse of get_peft_state_maybe_zero_3) and stay unmerged: generation
-    computes exactly what training computed.  No peft is needed.
+    computes exactly what training computed.  With merge_lora=True they are folded into the base weights after loading, as the
+    reference does (`Merging LoRA weights...`, model.merge_and_unload()): the model then runs LoRA-free, and tools/merge_lora_weights.py
+    writes it out as a full checkpoint.  No peft is needed.
   * a full checkpoint: LlavaLlamaForCausalLM.from_pretrained(model_path).
 
 Returns (tokenizer, model, image_processor, context_len).  The tokenizer is None when the tokenizer directory holds no tokenizer files.
@@ -100,7 +102,8 @@ def _base_with_config(model_base, model_path, dev):
     return model
 
 
-def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto", device="cuda", **kwargs):
+def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto", device="cuda",
+                          merge_lora=False, **kwargs):
     if load_8bit or load_4bit:
         raise NotImplementedError("8-bit / 4-bit loading is not supported: the model runs in bf16")
     dev = device
@@ -116,6 +119,9 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
                 grp.weight_cat_t = None          # (the transposed copy serves the training backward only)
         _load_projector(model, torch.load(os.path.join(model_path, "non_lora_trainables.bin"), map_location="cpu"))
         load_peft_state(model, torch.load(os.path.join(model_path, "adapter_model.bin"), map_location="cpu"))
+        if merge_lora:
+            print("Merging LoRA weights...")
+            model.merge_and_unload()
         tokenizer = _load_tokenizer(model_base)
     elif model_base is not None:
         # the projector alone over a base model (mm_projector.bin of a pretraining stage)

@@ -7,7 +7,11 @@ kernel alone at B = 16, H = 32, L = 2048 as effective TB/s (bytes = sum_b 2 L_b 
 384 px -> 196 image tokens after mlp_downsample, linear RoPE factor 2): one image + 60 text tokens, the attention kernel at H = 40,
 L = 4096.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--out profiles/r07_decode.json] [--steps 32]
+--merged: after the unmerged measurement the same model is merged in place (merge_and_unload: halva_lora_merge once per target) and
+the same decode steps are timed again; the record gains `merged` = {merge_s, weights_GB, decode}, next to the unmerged `weights_GB` /
+`decode` of the same run on the same box.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -124,6 +128,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--model", choices=("llava7b", "vila13b"), default="llava7b")
+    ap.add_argument("--merged", action="store_true", help="also time the decode step after merge_and_unload() on the same model")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
@@ -133,8 +138,20 @@ def main():
            "decode_attn": attn_kernel(H=40, L=4096) if vila else attn_kernel()}
     if not a.skip_model:
         m = model_vila13b() if vila else model_7b()
-        rec["weights_GB"] = round(sum(p.numel() * p.element_size() for n, p in m.named_parameters() if "vision_tower" not in n) / 1e9, 2)
-        rec["decode"] = decode_numbers(m, a.steps, text=60, image=384) if vila else decode_numbers(m, a.steps)
+        def weights_gb():
+            return round(sum(p.numel() * p.element_size() for n, p in m.named_parameters() if "vision_tower" not in n) / 1e9, 2)
+
+        def numbers():
+            return decode_numbers(m, a.steps, text=60, image=384) if vila else decode_numbers(m, a.steps)
+        rec["weights_GB"] = weights_gb()
+        rec["decode"] = numbers()
+        if a.merged:
+            import time
+            torch.cuda.synchronize()
+            t0 = time.time()
+            m.merge_and_unload()
+            torch.cuda.synchronize()
+            rec["merged"] = {"merge_s": round(time.time() - t0, 3), "weights_GB": weights_gb(), "decode": numbers()}
     line = json.dumps(rec)
     print(line)
     if a.out:

@@ -5,7 +5,8 @@ writes, local paths only.  The argument order is the reference's (model_path, mo
     mm_projector); model_path holds adapter_model.bin, non_lora_trainables.bin and adapter_config.json as
     vila/train/train_halva.py:save_lora_outputs writes them.  The projector comes from non_lora_trainables.bin; the factors of `.llm`'s
     adapter (`llm.base_model.model.model.layers.<i>.<sub>.<target>.lora_<A|B>.weight`) go back onto the LoraGroup factors and stay
-    unmerged (the reference merges them with peft; generation then computes what training computed).  No peft is needed.
+    unmerged (generation then computes what training computed); with merge_lora=True they are folded into the base weights after
+    loading, as the reference does with peft (`Merging LoRA weights...`, merge_and_unload()).  No peft is needed.
   * otherwise: a full VILA checkpoint directory.
 
 Returns (tokenizer, model, image_processor, context_len), the reference's tuple.  The tokenizer is None when the checkpoint's llm
@@ -55,7 +56,7 @@ def _build(path, dev):
 
 
 def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=False, load_4bit=False, device_map="auto", device="cuda",
-                          **kwargs):
+                          merge_lora=False, **kwargs):
     if load_8bit or load_4bit:
         raise NotImplementedError("8-bit / 4-bit loading is not supported: the model runs in bf16")
     dev = device
@@ -73,6 +74,9 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
         if os.path.exists(nl):
             load_projector(model, torch.load(nl, map_location="cpu"))
         load_vila_adapter(model, torch.load(os.path.join(model_path, "adapter_model.bin"), map_location="cpu"))
+        if merge_lora:
+            print("Merging LoRA weights...")
+            model.merge_and_unload()
     else:
         model = _build(model_path, dev)
     for p in model.parameters():
