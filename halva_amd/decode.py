@@ -1,4 +1,4 @@
-"""KV-cached greedy decoding for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) and VILA (VilaLlavaLlamaModel.generate) - forward only.
+"""KV-cached decoding (greedy, or temperature / top-k / top-p sampling) for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) and VILA (VilaLlavaLlamaModel.generate) - forward only.
 
 Stands in for the reference's HF `generate(..., use_cache=True)` decode path: the per-layer cache concat
 (llava/model/language_model/modelling_llama.py:295-305) and the decode position rule `attention_mask.sum(1) - 1`
@@ -101,15 +101,28 @@ def decode_step(model, cache, token_ids):
 
 
 # ------------------------------------------------------------------------------------------------
-# the greedy loop shared by both generate() methods
-def check_greedy_args(num_beams, do_sample, max_new_tokens):
-    """The call the reference's hallucination benchmarks make: do_sample=False, num_beams=1.  Anything else is refused."""
+# the generation loop shared by both generate() methods: greedy, or temperature / top-k / top-p sampling
+def check_generate_args(num_beams, do_sample, max_new_tokens, temperature=None, top_k=None, top_p=None):
+    """The calls the reference's hallucination benchmarks make: do_sample=False (greedy; temperature and top_p are ignored, as HF ignores
+    them) or do_sample=True with a temperature, both with num_beams=1.  -> None for greedy, (temperature, top_k, top_p) for sampling with
+    HF's GenerationConfig defaults filled in: top_k None = 50 (0 = off), top_p None = 1.0."""
     if num_beams is not None and num_beams > 1:
-        raise NotImplementedError("generate: beam search (num_beams=%d) is not implemented; greedy decoding only" % num_beams)
-    if do_sample:
-        raise NotImplementedError("generate: sampling (do_sample=True) is not implemented; greedy decoding only")
+        raise NotImplementedError("generate: beam search (num_beams=%d) is not implemented; greedy decoding and sampling only" % num_beams)
     if max_new_tokens is None or max_new_tokens < 1:
         raise ValueError("max_new_tokens must be >= 1")
+    if not do_sample:
+        return None
+    if temperature is None:
+        raise NotImplementedError("generate: sampling (do_sample=True) needs an explicit temperature: the model carries no "
+                                  "generation_config whose defaults could apply")
+    temperature, top_k, top_p = float(temperature), 50 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p)
+    if not (temperature > 0 and temperature != float("inf")):
+        raise ValueError("generate: temperature=%r (sampling needs a finite temperature > 0; do_sample=False decodes greedily)" % temperature)
+    if not 0 < top_p <= 1:
+        raise ValueError("generate: top_p=%r (needs 0 < top_p <= 1)" % top_p)
+    if top_k < 0:
+        raise ValueError("generate: top_k=%r (needs >= 0; 0 turns the cut off)" % top_k)
+    return temperature, top_k, top_p
 
 
 def eos_and_pad(config, eos_token_id, pad_token_id, device):
@@ -122,14 +135,10 @@ def eos_and_pad(config, eos_token_id, pad_token_id, device):
     return eos_ids, pad
 
 
-@torch.no_grad()
-def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria=None, prefix=None):
-    """Prefill, then argmax -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
-
-    A row that emitted an id of eos_ids is done and gets `pad` from then on.  stopping_criteria: a callable or a list of them (HF
-    StoppingCriteriaList semantics: any criterion that returns True stops the batch; a tensor it returns marks rows done), each called
-    after every step as criterion(seq, logits) with seq = cat(prefix, new tokens), or the new tokens alone when prefix is None.
-    One host sync per step."""
+def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix):
+    """Prefill, then select -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
+    select(logits [B, V] fp32) -> (next tokens [B], None) or (next tokens [B], bool [B] of rows it could not serve); with the latter the
+    flags ride on the step's one host sync and a set flag of a live row raises."""
     dev = inputs_embeds.device
     B = inputs_embeds.shape[0]
     crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
@@ -138,7 +147,9 @@ def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     out = []
     for step in range(max_new_tokens):
-        nxt = logits.argmax(-1)
+        nxt, bad = select(logits)
+        if bad is not None:
+            bad = bad & ~done
         nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
         out.append(nxt)
         if eos_ids.numel():
@@ -151,7 +162,47 @@ def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping
                     done = done | stop.to(dev, torch.bool).view(-1).expand(B)
                 elif stop:
                     done = torch.ones_like(done)
-        if step + 1 == max_new_tokens or bool(done.all()):          # the step's one host sync
-            break
+        if bad is None:
+            if step + 1 == max_new_tokens or bool(done.all()):          # the step's one host sync
+                break
+        else:
+            flags = torch.cat([done.all().view(1), bad]).tolist()       # the step's one host sync
+            if any(flags[1:]):
+                raise RuntimeError("generate: row %d has no token to sample at step %d (NaN or inf logits, or none above -inf)"
+                                   % (flags[1:].index(True), step))
+            if step + 1 == max_new_tokens or flags[0]:
+                break
         logits = decode_step(model, cache, nxt)
     return torch.stack(out, 1)
+
+
+@torch.no_grad()
+def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria=None, prefix=None):
+    """Prefill, then argmax -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
+
+    A row that emitted an id of eos_ids is done and gets `pad` from then on.  stopping_criteria: a callable or a list of them (HF
+    StoppingCriteriaList semantics: any criterion that returns True stops the batch; a tensor it returns marks rows done), each called
+    after every step as criterion(seq, logits) with seq = cat(prefix, new tokens), or the new tokens alone when prefix is None.
+    One host sync per step."""
+    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, lambda logits: (logits.argmax(-1), None),
+                          stopping_criteria, prefix)
+
+
+@torch.no_grad()
+def sample(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, temperature, top_k, top_p, generator=None, stopping_criteria=None,
+           prefix=None):
+    """As greedy(), with each step's token drawn from the temperature / top-k / top-p distribution of its logits by ONE native launch
+    (kernels.sample_top_k_top_p; top_k 0 = off, top_p 1 = off).  Each step draws u = torch.rand(B, generator=generator) on the device
+    exactly once, done rows included, so a row's stream does not depend on when other rows finish.  A live row whose logits leave nothing
+    to sample (NaN, inf) raises RuntimeError; the flag rides on the step's one host sync."""
+    dev = inputs_embeds.device
+    B = inputs_embeds.shape[0]
+    V = _stack(model).lm_head.shape[0]
+    if V > K.sample_max_vocab():
+        raise ValueError("generate: sampling takes a vocabulary of at most %d entries, the head has %d" % (K.sample_max_vocab(), V))
+
+    def select(logits):
+        u = torch.rand(B, device=dev, generator=generator)
+        tok = K.sample_top_k_top_p(logits, u, temperature, top_k, top_p)
+        return tok, tok < 0
+    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)

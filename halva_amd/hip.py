@@ -64,6 +64,8 @@ SIGNATURES = {
     "halva_decode_attn": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
     "halva_decode_attn_kc": [],
     "halva_decode_attn_chunked": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
+    "halva_sample_top_k_top_p": [_P, _L, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P],
+    "halva_sample_max_vocab": [],
 }
 
 

@@ -316,6 +316,30 @@ def decode_attention(q, kcache, vcache, lens, ws, H, D, out_width=None, ldq=None
     return out
 
 
+def sample_max_vocab():
+    """The widest row sample_top_k_top_p takes (a library constant)."""
+    return int(hip.load().halva_sample_max_vocab())
+
+
+def sample_top_k_top_p(logits, u, temperature, top_k, top_p, want_diag=False):
+    """One token per row of fp32 logits [B, V] (unit column stride, any row stride >= V) under temperature / top-k / top-p, drawn with the
+    caller's u [B] in [0, 1) (include/halva_hip.h:halva_sample_top_k_top_p) -> token int64 [B]; with want_diag also the threshold on the
+    scaled logit (fp32 [B]) and the size of the kept set (int32 [B]).  A row with a NaN or nothing above -inf gives -1."""
+    _chk(u, torch.float32, "u")
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise TypeError("logits must be a float32 device tensor, got %s on %s" % (logits.dtype, logits.device))
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1] or u.shape != (logits.shape[0],):
+        raise ValueError("sample_top_k_top_p: logits [B, V] with unit column stride and contiguous u [B]; got %s %s and %s"
+                         % (tuple(logits.shape), logits.stride(), tuple(u.shape)))
+    B, V = logits.shape
+    token = torch.empty(B, dtype=torch.int64, device=logits.device)
+    thr = torch.empty(B, dtype=torch.float32, device=logits.device) if want_diag else None
+    kept = torch.empty(B, dtype=torch.int32, device=logits.device) if want_diag else None
+    call("halva_sample_top_k_top_p", ptr(logits), logits.stride(0), ptr(u), ptr(token), ptr(thr),
+         ptr(kept), B, V, float(temperature), int(top_k), float(top_p), stream_ptr())
+    return (token, thr, kept) if want_diag else token
+
+
 def sdpa_full(qkv, H, D, scale=0.0):
     """Non-causal attention of the frozen CLIP / SigLIP tower (forward only).  qkv [N, S, 3*H*D] -> [N, S, H*D].
     scale 0 = 1/sqrt(D); SigLIP's 72-wide heads run zero-padded to D=128 with scale = 72**-0.5."""

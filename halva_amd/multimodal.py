@@ -185,12 +185,12 @@ class MultimodalMixin:
         return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
 
     @torch.no_grad()
-    def _generate_greedy(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                         stopping_criteria):
+    def _generate(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
+                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None):
         """The body of `generate`: the prompt is spliced when there are images, a tower and more than one token, else embedded;
-        then halva_amd/decode.py:greedy.  Right padding only."""
+        then halva_amd/decode.py:greedy, or :sample when do_sample is set.  Right padding only."""
         from . import decode as DEC
-        DEC.check_greedy_args(num_beams, do_sample, max_new_tokens)
+        sampling = DEC.check_generate_args(num_beams, do_sample, max_new_tokens, temperature, top_k, top_p)
         if input_ids is None or input_ids.ndim != 2:
             raise ValueError("generate needs input_ids [B, T]")
         dev = self.device
@@ -217,8 +217,10 @@ class MultimodalMixin:
         if int(seq_start.max()) != 0:
             raise NotImplementedError(_LEFT_PADDED)
         eos_ids, pad = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, dev)
-        if not self.generate_returns_prompt:
-            return DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=None)
-        prompt = input_ids.to(dev)
-        out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt)
-        return torch.cat([prompt.long(), out], 1)
+        prompt = input_ids.to(dev) if self.generate_returns_prompt else None
+        if sampling is None:
+            out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt)
+        else:
+            out = DEC.sample(self, embeds, seq_len, max_new_tokens, eos_ids, pad, *sampling, generator=generator,
+                             stopping_criteria=stopping_criteria, prefix=prompt)
+        return out if prompt is None else torch.cat([prompt.long(), out], 1)

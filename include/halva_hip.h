@@ -314,6 +314,24 @@ int64_t halva_decode_attn_ws_bytes(int B, int H, int Lcap);
 int halva_decode_attn_chunked(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out,
                               int64_t ld_out, void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, int kc, void* stream);
 
+/* ---- Sampling (generate with do_sample=True, halva_amd/decode.py:sample).  replaces what HF's generate runs per step behind the reference's
+ * `model.generate(..., do_sample=True, temperature=args.temperature, top_p=args.top_p, ...)` (eval_hall/model_chair_loader.py:124-130):
+ * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper(min_tokens_to_keep=1) -> softmax -> torch.multinomial, i.e. about ten
+ * launches and a [B, V] sort, as ONE launch without a sort (one workgroup per row, the row read once and held in registers).
+ *   logits fp32 [B, V], row stride ld >= V elements (columns [V, ld) are never read); u fp32 [B] on the device, each in [0, 1) - the
+ *   caller's random numbers, the kernel holds no generator; temperature > 0; top_k >= 0 (0 = off); 0 < top_p <= 1.
+ * With x_i = l_i / temperature:  K1 = { i : x_i > -inf and #{ j : x_j > x_i } < top_k }  (top_k = 0 or >= V: every x_i > -inf);
+ * p = softmax of x over K1;  K2 = { i in K1 : sum_{j in K1, x_j > x_i} p_j < top_p }  (top_p = 1: K1).  K2 is never empty and always
+ * { i : x_i >= thr }: ties at either cut are all kept, as in HF.  With q = p renormalised over K2, token[b] = the first column k of K2, in
+ * ascending column order, with sum_{i in K2, i <= k} q_i > u[b]; the last column of K2 when rounding leaves none.
+ * token int64 [B]; thr fp32 [B] (the threshold on x) and kept int32 [B] (|K2|) are diagnostics, NULL allowed.  A row that holds a NaN or
+ * +inf, or nothing above -inf, gets token -1, kept 0, thr NaN; other rows are unaffected.  Every sum runs in one fixed order that depends on
+ * V alone and there are no float atomics: row b's outputs are bitwise the same in any batch and at any row position.
+ * V <= halva_sample_max_vocab() (32768, what the registers of one 1024-lane workgroup hold); larger V is HALVA_ERR_INVALID_ARG. */
+int halva_sample_top_k_top_p(const float* logits, int64_t ld, const float* u, int64_t* token, float* thr, int32_t* kept, int B, int V,
+                             float temperature, int top_k, float top_p, void* stream);
+int halva_sample_max_vocab(void);
+
 /* ---- hardware-layout probes used by the GPU tests (MFMA fragment maps, ds_read_b64_tr_b16). */
 int halva_probe_layouts(int32_t* out, int n, void* stream);
 /* ---- measurement aid (bench.py's clock trace; no reference counterpart): `blocks` one-wave workgroups each spin for `spin_ticks` ticks of

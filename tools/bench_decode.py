@@ -11,7 +11,11 @@ L = 4096.
 the same decode steps are timed again; the record gains `merged` = {merge_s, weights_GB, decode}, next to the unmerged `weights_GB` /
 `decode` of the same run on the same box.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--out profiles/r07_decode.json] [--steps 32]
+--sample: the record gains `sample`: at V = 32000 and B = 1 and 16, us per call of the native token select (halva_sample_top_k_top_p)
+and of the torch composition it stands in for (softmax, sort, cumsum, scatter, softmax, multinomial, as HF's warpers run them) on the same
+logits, and ms per step of the whole sampled loop (decode.sample) beside the greedy loop (decode.greedy) on the same prompts.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -122,6 +126,72 @@ def decode_numbers(m, steps, text=64, image=336):
     return res
 
 
+SAMPLE_SETTINGS = ((0.2, 50, 0.7), (1.0, 0, 0.9))      # (temperature, top_k, top_p): the scripts' call with HF's top_k, and top-p alone
+
+
+def torch_select(logits, temperature, top_k, top_p):
+    """HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax -> multinomial, restated in torch."""
+    s = logits / temperature
+    if top_k > 0:
+        s = s.masked_fill(s < torch.topk(s, top_k)[0][..., -1, None], -float("inf"))
+    if top_p < 1.0:
+        sl, si = torch.sort(s, descending=False)
+        remove = sl.softmax(-1).cumsum(-1) <= 1 - top_p
+        remove[..., -1:] = False
+        s = s.masked_fill(remove.scatter(1, si, remove), -float("inf"))
+    return torch.multinomial(s.softmax(-1), 1).squeeze(1)
+
+
+def select_numbers(V=32000, reps=200):
+    from halva_amd import kernels as K
+    res = {}
+    for B in (1, 16):
+        logits = (8.0 * torch.randn(B, V, device="cuda")).bfloat16().float()
+        u = torch.rand(B, device="cuda")
+        for T, k, p in SAMPLE_SETTINGS:
+            native = _time(lambda: K.sample_top_k_top_p(logits, u, T, k, p), reps, warmup=10)
+            composed = _time(lambda: torch_select(logits, T, k, p), reps, warmup=10)
+            res["B%d_T%g_k%d_p%g" % (B, T, k, p)] = {"native_us": round(native * 1e3, 2), "torch_us": round(composed * 1e3, 2)}
+    return {"V": V, "by_setting": res}
+
+
+def loop_numbers(m, steps, text=64, image=336):
+    """ms per step of the whole loop, host syncs included: (a run of steps + 1 tokens - a run of 1 token) / steps."""
+    import time
+    from halva_amd import decode as DEC
+    g = torch.Generator().manual_seed(0)
+    T_, k, p = SAMPLE_SETTINGS[0]
+    none = torch.empty(0, dtype=torch.long, device="cuda")
+    res = {}
+    for B in (1, 16):
+        ids = torch.randint(3, 32000, (B, text), generator=g)
+        ids[:, 0] = 1
+        ids[:, 6] = -200
+        images = torch.randn(B, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+        with torch.no_grad():
+            embeds, plan = m._splice(ids.cuda(), None, None, None, images)
+
+        def wall(fn, n):
+            best = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(n)
+                torch.cuda.synchronize()
+                best.append(time.perf_counter() - t0)
+            return statistics.median(best) * 1e3
+
+        def greedy(n):
+            DEC.greedy(m, embeds, plan.seq_len, n, none, 0)
+
+        def sampled(n):
+            DEC.sample(m, embeds, plan.seq_len, n, none, 0, T_, k, p)
+        greedy(2), sampled(2)
+        res["B%d" % B] = {"greedy_ms_per_step": round((wall(greedy, steps + 1) - wall(greedy, 1)) / steps, 3),
+                          "sampled_ms_per_step": round((wall(sampled, steps + 1) - wall(sampled, 1)) / steps, 3)}
+    return {"temperature": T_, "top_k": k, "top_p": p, "loop": res}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -129,6 +199,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--model", choices=("llava7b", "vila13b"), default="llava7b")
     ap.add_argument("--merged", action="store_true", help="also time the decode step after merge_and_unload() on the same model")
+    ap.add_argument("--sample", action="store_true", help="also time the native token select, its torch composition and the sampled loop")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
@@ -136,6 +207,8 @@ def main():
     vila = a.model == "vila13b"
     rec = {"device": torch.cuda.get_device_name(0), "model": a.model,
            "decode_attn": attn_kernel(H=40, L=4096) if vila else attn_kernel()}
+    if a.sample:
+        rec["sample"] = select_numbers()
     if not a.skip_model:
         m = model_vila13b() if vila else model_7b()
         def weights_gb():
@@ -145,6 +218,8 @@ def main():
             return decode_numbers(m, a.steps, text=60, image=384) if vila else decode_numbers(m, a.steps)
         rec["weights_GB"] = weights_gb()
         rec["decode"] = numbers()
+        if a.sample:
+            rec["sample"].update(loop_numbers(m, a.steps, text=60, image=384) if vila else loop_numbers(m, a.steps))
         if a.merged:
             import time
             torch.cuda.synchronize()
