@@ -116,15 +116,12 @@ def _wgrad_operands(C, A, B):
 def wgrad_accumulate(C, A, B, alpha=1.0):
     """C [M, N] f32 += alpha * A^T B for bf16 column windows A [rows, M], B [rows, N] of wider row-major buffers (LoRA weight
     gradients, include/halva_hip.h:halva_wgrad_accumulate).  Split over the rows; partials are summed in a fixed order."""
-    rows, M, N = _wgrad_operands(C, A, B)
-    ws = _wgrad_workspace(C.device)
-    call("halva_wgrad_accumulate", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), M, N, rows, float(alpha), ptr(ws), ws.numel(),
-         stream_ptr())
+    wgrad_accumulate_batch([(C, A, B, alpha)])
 
 
 def wgrad_accumulate_batch(items):
     """[(C, A, B, alpha), ...] -> every C [M, N] f32 += alpha * A^T B, as ONE launch pair for the two to four products of a LoRA group
-    (include/halva_hip.h:halva_wgrad_accumulate_batch); bitwise the results of wgrad_accumulate called once per item."""
+    (include/halva_hip.h:halva_wgrad_accumulate_batch: longer lists are cut into chunks there); bitwise the results of one call per item."""
     ws = _wgrad_workspace(items[0][0].device)
     arr = (hip.WgradItem * len(items))()
     for it, (C, A, B, alpha) in zip(arr, items):

@@ -67,7 +67,7 @@ def _jsonable(v):
 # memory once more (13.5 GB at 7B, 26 GB at 13B - of 288 GB); HALVA_DGRAD_WT=0 turns it off.
 DGRAD_TRANSPOSED_COPY = os.environ.get("HALVA_DGRAD_WT", "1") != "0"
 WGRAD_KERNEL = os.environ.get("HALVA_WGRAD_KERNEL", "1") != "0"      # LoRA weight gradients through halva_wgrad_accumulate
-WGRAD_BATCH = os.environ.get("HALVA_WGRAD_BATCH", "1") != "0"        # ... the factors of a group as ONE launch pair (round 6; 0 = one pair per factor, bitwise the same)
+WGRAD_BATCH = os.environ.get("HALVA_WGRAD_BATCH", "1") != "0"        # ... the factors of a group as ONE call (round 6; 0 = one call per factor, bitwise the same)
 RES_INPLACE = os.environ.get("HALVA_RES_INPLACE", "1") != "0"        # residual adds accumulate onto the block's own buffer (A/B: 0)
 # dgrad through the MERGED weight: the transposed copy holds (W + scale * B A)^T, so dx = dy (W + scale B A) comes out of the one
 # dgrad GEMM complete and the separate dx += (scale * dy B) A pass over [rows, in] is gone (A/B: 0)
@@ -148,38 +148,26 @@ class _LoraGroupFn(torch.autograd.Function):
             # Weight gradients of the factors: one side of each product is only r..G r wide and the contraction runs over every token
             # row, a shape the library serves with 32-86 tiles.  With an f32 sink they go through the split-k kernel
             # (halva_wgrad_accumulate: 76 vs 136 us for a [4096 x 128] factor at 27 k rows), straight into main_grad.
-            fused = (sink and WGRAD_KERNEL and all(t.main_grad.is_contiguous() and t.main_grad.data_ptr() % 16 == 0 and
-                                                   t.main_grad.dtype == torch.float32 for t in (A, *Bs))
-                     and K_.wgrad_supported(da, xa2[:, :K]) and K_.wgrad_supported(dy2[:, :Bs[0].shape[0]], xa2[:, K:K + r]))
-            batch = [] if (fused and WGRAD_BATCH and len(Bs) <= 3) else None      # (the A factor + up to three B factors: one launch pair)
-            if batch is not None:
-                batch.append((A.main_grad, da, xa2[:, :K], 1.0))
-            elif fused:
-                K_.wgrad_accumulate(A.main_grad, da, xa2[:, :K], 1.0)
-            else:
-                gA = torch.mm(da.t(), xa2[:, :K])
-            off = 0
+            # One list of products (parameter, left, right, factor): grad = factor * left^T right.  Exactly one sink takes it.
+            prods, off = [(A, da, xa2[:, :K], 1.0)], 0
             for g, B in enumerate(Bs):
                 n = B.shape[0]
-                if batch is not None:
-                    batch.append((B.main_grad, dy2[:, off:off + n], xa2[:, K + g * r:K + (g + 1) * r], scale))
-                elif fused:
-                    K_.wgrad_accumulate(B.main_grad, dy2[:, off:off + n], xa2[:, K + g * r:K + (g + 1) * r], scale)
-                else:
-                    gB = torch.mm(dy2[:, off:off + n].t(), xa2[:, K + g * r:K + (g + 1) * r])
-                    if sink:
-                        B.main_grad.add_(gB, alpha=scale)
-                    else:
-                        dBs[g] = gB * scale
+                prods.append((B, dy2[:, off:off + n], xa2[:, K + g * r:K + (g + 1) * r], scale))
                 off += n
-            if batch is not None:
-                K_.wgrad_accumulate_batch(batch)
-            if fused:
-                pass
+            if sink and WGRAD_KERNEL and all(P.main_grad.is_contiguous() and P.main_grad.data_ptr() % 16 == 0 and P.main_grad.dtype == torch.float32
+                                             and K_.wgrad_supported(L, R) for P, L, R, _ in prods):
+                items = [(P.main_grad, L, R, f) for P, L, R, f in prods]
+                if WGRAD_BATCH:                             # (the whole group as one call: one launch pair per chunk of up to four products)
+                    K_.wgrad_accumulate_batch(items)
+                else:
+                    for it in items:
+                        K_.wgrad_accumulate(*it)
             elif sink:
-                A.main_grad.add_(gA)
+                for P, L, R, f in prods:
+                    P.main_grad.add_(torch.mm(L.t(), R), alpha=f)
             else:
-                dA = gA
+                gA, *gBs = [torch.mm(L.t(), R) for _, L, R, _ in prods]
+                dA, dBs = gA, [gB * scale for gB in gBs]
             if not merged:                                  # (merged: WcT's base rows already hold (W + scale B A)^T, LoraGroup.refresh_tail)
                 dxa[:, :K].addmm_(da, A)                    # + the LoRA path's contribution to dx, in place
         else:

@@ -171,14 +171,16 @@ int halva_gemm_bf16(const void* A, const void* B, const void* bias, void* C, voi
  * dA = (scale * dy B)^T x.  One side of the product is 128..384 wide, the contraction runs over all token rows, so the library
  * GEMM has 32-86 tiles for 256 CUs; here the rows are split into k-slabs (partials in ws, summed in a fixed order - no atomics).
  * ws: scratch of ws_floats >= M * N floats; the number of slabs is what fits, up to one resident
- * round of workgroups (512). */
+ * round of workgroups (512).  This is halva_wgrad_accumulate_batch with one item. */
 int halva_wgrad_accumulate(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int M, int N, int64_t rows, float alpha,
                            float* ws, int64_t ws_floats, void* stream);
 /* The same for the two to four products of ONE LoRA group at once (its A factor and its B factors: they become available together in the group's
  * backward - halva_amd/llama.py:_LoraGroupLinear, i.e. peft's LoRA linear backward as used by llava/train/train_halva.py:1085-1101): one launch of
  * the tile kernel and one of the reduction instead of two per product.  Results are BITWISE those of halva_wgrad_accumulate called once per item
- * with the same workspace (same k-slabs, same summation order); items that the batched kernel does not take (more than 4, shapes that are no
- * multiples of 128, partials that do not fit the workspace side by side) simply run one by one.  items: HOST array of n descriptors. */
+ * with the same workspace (same k-slabs, same summation order).  The items are cut in order into chunks of at most 4 whose partials fit the
+ * workspace side by side; a chunk whose every item takes the LDS-DMA tile kernel (M and N multiples of 128) is one tile launch, any other chunk one
+ * tile launch per item; every chunk ends with one launch of the reduction.  ALL items are validated before anything is launched: an invalid item
+ * returns HALVA_ERR_INVALID_ARG with its index in the message and no C of any item has been touched.  items: HOST array of n descriptors. */
 typedef struct halva_wgrad_item {
     const void* A;      /* [rows, M] bf16 window, row stride lda */
     int64_t lda;

@@ -1,4 +1,4 @@
-"""Elementwise checks of halva_amd/csrc/gemm.hip against float64, with poisoned surroundings: halva_gemm_bf16 in its three forms
+"""Elementwise checks of halva_amd/csrc/gemm.hip (gemm_tile.h, wgrad.h) against float64, with poisoned surroundings: halva_gemm_bf16 in its three forms
 and every argument combination, halva_wgrad_accumulate(_batch), halva_transpose_bf16, halva_colsum, halva_gelu_bwd.
 
 test_hip_kernels.py takes one relative Frobenius error (or one maximum error scaled by the row count) per tensor.  Here every element
@@ -58,12 +58,17 @@ def _wgrad(A, B, C, rows, alpha, ws, ws_floats):
     call("halva_wgrad_accumulate", ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), M, N, rows, float(alpha), ptr(ws), ws_floats, stream_ptr())
 
 
-def _wgrad_batch(items, ws, ws_floats):
+def _wgrad_items(items):
     arr = (hip.WgradItem * len(items))()
     for it, (C, A, B, alpha) in zip(arr, items):
         it.A, it.lda, it.B, it.ldb, it.C, it.M, it.N, it.rows, it.alpha = ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.shape[0], C.shape[1], \
             A.shape[0], float(alpha)
-    call("halva_wgrad_accumulate_batch", len(items), ctypes.cast(arr, ctypes.c_void_p), ptr(ws), ws_floats, stream_ptr())
+    return arr
+
+
+def _wgrad_batch(items, ws, ws_floats):
+    arr = items if isinstance(items, ctypes.Array) else _wgrad_items(items)
+    call("halva_wgrad_accumulate_batch", len(arr), ctypes.cast(arr, ctypes.c_void_p), ptr(ws), ws_floats, stream_ptr())
 
 
 def _transpose(src, dst, rows, cols):
@@ -197,7 +202,7 @@ def test_gemm_tn_without_trans_b_is_an_argument_error():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # halva_wgrad_accumulate
 def wgrad_slabs(M, N, rows, ws_floats):
-    """the split of gemm.hip's wgrad_slabs, restated (only the bound's operation count uses it)"""
+    """the split of wgrad.h's wgrad_slabs, restated (only the bound's operation count uses it)"""
     tiles = -(-M // 128) * -(-N // 128)
     splits = max(1, min(64, 512 // tiles, ws_floats // (M * N)))
     ksplit = (-(-rows // splits) + 63) // 64 * 64
@@ -334,6 +339,93 @@ def test_wgrad_batch_elementwise(group, regime):
         worst = max(worst, _check_wgrad("wgrad batch %s item %d" % (group, i), C, C0, Aw, Bw, alpha, regime, wgrad_slabs(M, N, rows, ws_floats)[0]))
     if regime == "random":
         print("[wgrad batch %s] worst error / bound %.3f" % (group, worst))
+
+
+# One planned path: both entry points run wgrad.h's wgrad_run, which cuts a call's items in order into chunks of at most four whose
+# partials fit the workspace side by side.  "Batch equals one call per item" therefore compares two routes through the same kernels; what
+# holds the result independently is the float64 bound on every item here and the register-staged kernel's bits (HALVA_WGRAD_DMA=0).
+CHUNK_ROWS = 200                        # ends 8 rows into a 64-row tile
+T128 = 128 * 128
+CHUNK_CASES = {"six": ([(128, 128), (128, 256), (256, 128), (8, 8), (128, 128), (128, 128)], 48 * 2 ** 20),      # more than four items
+               "mixed": ([(128, 256), (8, 8), (256, 128)], 48 * 2 ** 20),                                      # LDS-DMA and register-staged items in one chunk
+               "ws9": ([(128, 128)] * 3, 9 * T128),     # 4 slabs each (200 rows / 64): two items side by side, the third opens a chunk
+               "ws5": ([(128, 128)] * 3, 5 * T128),     # every item its own chunk
+               "three": ([(128, 128)] * 3, 48 * 2 ** 20)}
+
+
+def _batch_against_single_calls(case, regime):
+    """the case's items through ONE batch call: nothing written around any C or the workspace, every item the bits of a call of its own
+    with the same workspace size and held to float64 -> the batch call's results"""
+    shapes, ws_floats = CHUNK_CASES[case]
+    rows, g = CHUNK_ROWS, _gen(len(case))
+    items = []
+    for i, (M, N) in enumerate(shapes):
+        Aw, Bw, C0 = _windows(rows, M, N, M + 16, N + 32, regime, g, i)
+        items.append((C0, Aw, Bw, (1.0, 0.5, 0.25)[i % 3]))
+    full, ws = _framed_ws(ws_floats)
+    one = []
+    for C0, Aw, Bw, alpha in items:
+        one.append(C0.clone())
+        _wgrad(Aw, Bw, one[-1], rows, alpha, ws, ws_floats)
+        torch.cuda.synchronize()
+        assert _ws_intact(full, ws_floats), (case, "floats around the workspace were written")
+    framed = [embed(C0, SENT, rows_before=_guard(C0.shape[1]), rows_after=_guard(C0.shape[1])) for C0, _, _, _ in items]
+    before = [f[0].clone() for f in framed]
+    _wgrad_batch([(f[1], Aw, Bw, alpha) for f, (_, Aw, Bw, alpha) in zip(framed, items)], ws, ws_floats)
+    torch.cuda.synchronize()
+    assert _ws_intact(full, ws_floats), (case, "floats around the workspace were written")
+    for i, ((cbuf, C), cb, (C0, Aw, Bw, alpha)) in enumerate(zip(framed, before, items)):
+        M, N = C0.shape
+        splits = wgrad_slabs(M, N, rows, ws_floats)[0]
+        assert splits * M * N <= ws_floats
+        assert outside_unchanged(cbuf, cb, _guard(N), M, 0, N), (case, i, "bytes around C were written")
+        assert torch.equal(C, one[i]), (case, i, "the batch differs from one call per item")
+        _check_wgrad("wgrad chunks %s item %d" % (case, i), C, C0, Aw, Bw, alpha, regime, splits)
+    return [C.clone() for _, C in framed]
+
+
+@pytest.mark.parametrize("regime", ["exact", "random"])
+@pytest.mark.parametrize("case", ["six", "mixed", "ws9", "ws5"])
+def test_wgrad_batch_chunks(case, regime):
+    """More items than one table holds, a chunk boundary forced by the workspace, and a chunk whose items take different tile kernels."""
+    if case in ("ws9", "ws5"):
+        assert wgrad_slabs(128, 128, CHUNK_ROWS, CHUNK_CASES[case][1])[0] == 4
+    _batch_against_single_calls(case, regime)
+
+
+@pytest.mark.parametrize("regime", ["exact", "random"])
+def test_wgrad_batch_ab_kernels(regime, monkeypatch):
+    """The register-staged kernel and the four-stage LDS-DMA kernel through the batch entry: the bits of the default run."""
+    monkeypatch.delenv("HALVA_WGRAD_DMA", raising=False)
+    monkeypatch.delenv("HALVA_WGRAD_KT", raising=False)
+    default = _batch_against_single_calls("three", regime)
+    for name, value in (("HALVA_WGRAD_DMA", "0"), ("HALVA_WGRAD_KT", "32")):
+        with monkeypatch.context() as m:
+            m.setenv(name, value)
+            got = _batch_against_single_calls("three", regime)
+        for i, (a, b) in enumerate(zip(got, default)):
+            assert torch.equal(a, b), ("%s=%s differs from the default run's bits" % (name, value), i)
+
+
+@pytest.mark.parametrize("bad_lda", [128 - 8, 128 + 4], ids=["lda-below-M", "lda-not-8"])
+def test_wgrad_batch_validates_every_item_before_any_launch(bad_lda):
+    """An invalid item 2 (its row stride does not cover M / is no multiple of 8): the error names it, and items 0 and 1 - valid, and
+    ahead of it - have NOT been added into their C.  (Every pointer is a live allocation; nothing here reaches a kernel.)"""
+    rows, ws_floats, g = CHUNK_ROWS, 48 * T128, _gen(7)
+    items = []
+    for i in range(3):
+        Aw, Bw, C0 = _windows(rows, 128, 128, 144, 160, "random", g, i)
+        items.append((C0.clone(), Aw, Bw, 1.0))
+    arr = _wgrad_items(items)
+    arr[2].lda = bad_lda
+    full, ws = _framed_ws(ws_floats)
+    before = [C.clone() for C, _, _, _ in items]
+    with pytest.raises(HalvaHipError, match="item 2"):
+        _wgrad_batch(arr, ws, ws_floats)
+    torch.cuda.synchronize()
+    for i, ((C, _, _, _), b) in enumerate(zip(items, before)):
+        assert same_bits(C, b), ("item %d's C was touched by a call that failed" % i)
+    assert bool((full == SENT).all()), "the workspace was written by a call that failed"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -825,7 +825,8 @@ def test_wgrad_batch_gives_the_bits_of_one_call_per_factor(group):
     """halva_wgrad_accumulate_batch (round 6): the A factor and the B factors of ONE LoRA group as one launch of the tile
     kernel + one of the reduction - with the slab counts of the single-problem call, so the partials, their order and the results are the bits of
     halva_wgrad_accumulate called once per factor (peft's LoRA linear backward as used by llava/train/train_halva.py:1085-1101).  The shapes of the
-    7B step's four groups at the packed bench rows; "odd_shapes": items the batched kernel does not take run one by one inside the same call."""
+    7B step's four groups at the packed bench rows; "odd_shapes": items the LDS-DMA table kernel does not take get one register-staged
+    tile launch each, into their own regions of the workspace, and share the one reduction."""
     rows, d, F, r = 27424, 4096, 11008, 128
     shapes = {"qkv_7b": [(3 * r, d)] + [(d, r)] * 3, "gate_up_7b": [(2 * r, d)] + [(F, r)] * 2, "o_7b": [(r, d), (d, r)], "down_7b": [(r, F), (d, r)],
               "odd_shapes": [(320, 1032), (8, 8)]}[group]
