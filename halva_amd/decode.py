@@ -49,6 +49,14 @@ class KVCache:
             lm._rope = {}
             cos, sin = lm.rope(Lcap, dev)
         self.cos, self.sin = cos, sin
+        self._ext_ws = None        # the extend attention's workspace: allocated on first use (extend_ws), so a cache that is never extended keeps its size
+
+    def extend_ws(self, n):
+        """The workspace of kernels.extend_attention for blocks of n rows, allocated (or grown) on first use."""
+        need = max(K.extend_ws_bytes(self.B, n, self.H, self.Lcap), 16)
+        if self._ext_ws is None or self._ext_ws.numel() < need:
+            self._ext_ws = torch.empty(need, dtype=torch.uint8, device=self.k[0].device)
+        return self._ext_ws
 
     def fill(self, layer_idx, qkv, seq_len):
         """Prompt pass: the rotated k and the plain v of the [B, T, 3*H*D] projection into slots [0, T) (rows past seq_len[b] are
@@ -100,6 +108,82 @@ def decode_step(model, cache, token_ids):
     return _lm_head(st, lm.norm(x))
 
 
+@torch.no_grad()
+def extend(model, cache, inputs_embeds, n_new):
+    """Several new rows per sequence in one pass over a cache that already holds rows: inputs_embeds [B, n, d], n_new [B] host ints with
+    0 <= n_new[b] <= n (sequence b pushes its rows [0, n_new[b]) at positions lens[b] ..) -> logits [B, V] fp32 of each sequence's last new
+    row.  A sequence with n_new[b] == 0 is left as it is (cache and lens untouched) and gets NaN logits: callers mask them.  Every check
+    runs before the first launch; a block that does not fit raises RuntimeError like decode_step's."""
+    from .llama import TOP_ROWS
+    st = _stack(model)
+    lm = st.lm
+    if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != cache.B:
+        raise ValueError("extend needs inputs_embeds [B=%d, n, d], got %s" % (cache.B, tuple(inputs_embeds.shape)))
+    B, n, _ = inputs_embeds.shape
+    n_new = torch.as_tensor(n_new, dtype=torch.int32).view(-1).cpu()
+    if n_new.numel() != B:
+        raise ValueError("extend needs one n_new per sequence (%d), got %d" % (B, n_new.numel()))
+    most = int(n_new.max())
+    if most < 1 or int(n_new.min()) < 0 or most > n:
+        raise ValueError("extend: every n_new[b] must lie in [0, n=%d] and one of them must be >= 1, got %s" % (n, n_new.tolist()))
+    if cache.filled + most > min(cache.Lcap, cache.cos.shape[0]):
+        raise RuntimeError("KV cache full: %d slots used of %d, %d more asked for; allocate the cache for the prompt plus every new row"
+                           % (cache.filled, cache.Lcap, most))
+    cache.filled += most
+    dev = lm.embed_tokens.weight.device
+    n_new_d = n_new.to(dev)
+    rows = (torch.arange(B, dtype=torch.int64) * n + (n_new.long() - 1).clamp_(min=0)).to(dev)
+    x = inputs_embeds.to(dev, torch.bfloat16, copy=True).contiguous()      # a buffer of our own: the residual adds run on it in place
+    last = len(lm.layers) - 1
+    for i, layer in enumerate(lm.layers):
+        top = rows if (TOP_ROWS and i == last) else None
+        x = layer.extend(x, cache, i, n_new_d, st.use_lora, top)
+        if top is not None:
+            rows = None
+    x = lm.norm(x)
+    if rows is not None:
+        x = x.view(-1, x.shape[-1]).index_select(0, rows)
+    return _lm_head(st, x).masked_fill_((n_new_d == 0)[:, None], float("nan"))
+
+
+def chunk_schedule(seq_len, T, chunk):
+    """How prefill_chunked cuts right-padded prompts of seq_len[b] rows (T columns) into blocks of `chunk` rows: a list of
+    (first column, columns, n_new [B]).  Block 0 is the prefill() call (n_new = seq_len clipped to its columns); blocks that hold only
+    padding are dropped."""
+    seq_len = [int(v) for v in seq_len]
+    if chunk is None or int(chunk) < 1:
+        raise ValueError("prefill_chunk must be an int >= 1, got %r" % (chunk,))
+    chunk = int(chunk)
+    out, done = [], 0
+    while done < max(seq_len) or not out:
+        n = min(chunk, T - done)
+        out.append((done, n, [min(max(v - done, 0), n) for v in seq_len]))
+        done += n
+    return out
+
+
+@torch.no_grad()
+def prefill_chunked(model, inputs_embeds, seq_len, cache, chunk):
+    """prefill() in blocks of `chunk` rows, so that no pass holds more than [B, chunk, .] activations: the first block through prefill(),
+    the others through extend() over the rows the cache already holds.  -> each sequence's last-prompt-row logits [B, V] fp32, taken from
+    the block in which that sequence ended."""
+    B, T, _ = inputs_embeds.shape
+    seq_len = torch.as_tensor(seq_len, dtype=torch.int32).cpu()
+    if int(seq_len.min()) < 1 or int(seq_len.max()) > T:
+        raise ValueError("every prompt needs between 1 and T=%d rows" % T)
+    logits = None
+    for start, n, n_new in chunk_schedule(seq_len.tolist(), T, chunk):
+        block = inputs_embeds[:, start:start + n].contiguous()
+        if start == 0:
+            logits = prefill(model, block, torch.tensor(n_new, dtype=torch.int32), cache)
+            cache.filled = max(n_new)          # (fill() counts the block's columns; nothing beyond the longest prompt's rows is ever read)
+        else:
+            lg = extend(model, cache, block, n_new)
+            live = torch.tensor([v > 0 for v in n_new], device=lg.device)
+            logits = torch.where(live[:, None], lg, logits)
+    return logits
+
+
 # ------------------------------------------------------------------------------------------------
 # the generation loop shared by both generate() methods: greedy, or temperature / top-k / top-p sampling
 def check_generate_args(num_beams, do_sample, max_new_tokens, temperature=None, top_k=None, top_p=None):
@@ -135,19 +219,32 @@ def eos_and_pad(config, eos_token_id, pad_token_id, device):
     return eos_ids, pad
 
 
-def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix):
+def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, prefill_chunk=None):
     """Prefill, then select -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
     select(logits [B, V] fp32) -> (next tokens [B], None) or (next tokens [B], bool [B] of rows it could not serve); with the latter the
-    flags ride on the step's one host sync and a set flag of a live row raises."""
-    dev = inputs_embeds.device
+    flags ride on the step's one host sync and a set flag of a live row raises.  prefill_chunk: None = one prompt pass, an int = the
+    prompt pass in blocks of that many rows (prefill_chunked)."""
     B = inputs_embeds.shape[0]
+    cache = KVCache(model, B, inputs_embeds.shape[1] + max_new_tokens, inputs_embeds.device)
+    if prefill_chunk is None:
+        logits = prefill(model, inputs_embeds, seq_len, cache)
+    else:
+        logits = prefill_chunked(model, inputs_embeds, seq_len, cache, prefill_chunk)
+    return _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)[0]
+
+
+def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix):
+    """_generate_loop's steps from a given (cache, logits [B, V]) -> (new tokens [B, n], real [B] on the device: how many of a row's n
+    tokens it selected while live, the others being pad).  The last selected token is not pushed through the model."""
+    dev = logits.device
+    B = logits.shape[0]
     crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
-    cache = KVCache(model, B, inputs_embeds.shape[1] + max_new_tokens, dev)
-    logits = prefill(model, inputs_embeds, seq_len, cache)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
+    real = torch.zeros(B, dtype=torch.int64, device=dev)
     out = []
     for step in range(max_new_tokens):
         nxt, bad = select(logits)
+        real = real + ~done
         if bad is not None:
             bad = bad & ~done
         nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
@@ -173,30 +270,37 @@ def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, 
             if step + 1 == max_new_tokens or flags[0]:
                 break
         logits = decode_step(model, cache, nxt)
-    return torch.stack(out, 1)
+    return torch.stack(out, 1), real
+
+
+def _argmax(logits):
+    return logits.argmax(-1), None
 
 
 @torch.no_grad()
-def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria=None, prefix=None):
+def greedy(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria=None, prefix=None, prefill_chunk=None):
     """Prefill, then argmax -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
 
     A row that emitted an id of eos_ids is done and gets `pad` from then on.  stopping_criteria: a callable or a list of them (HF
     StoppingCriteriaList semantics: any criterion that returns True stops the batch; a tensor it returns marks rows done), each called
     after every step as criterion(seq, logits) with seq = cat(prefix, new tokens), or the new tokens alone when prefix is None.
     One host sync per step."""
-    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, lambda logits: (logits.argmax(-1), None),
-                          stopping_criteria, prefix)
+    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, _argmax, stopping_criteria, prefix, prefill_chunk)
 
 
 @torch.no_grad()
 def sample(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, temperature, top_k, top_p, generator=None, stopping_criteria=None,
-           prefix=None):
+           prefix=None, prefill_chunk=None):
     """As greedy(), with each step's token drawn from the temperature / top-k / top-p distribution of its logits by ONE native launch
     (kernels.sample_top_k_top_p; top_k 0 = off, top_p 1 = off).  Each step draws u = torch.rand(B, generator=generator) on the device
     exactly once, done rows included, so a row's stream does not depend on when other rows finish.  A live row whose logits leave nothing
     to sample (NaN, inf) raises RuntimeError; the flag rides on the step's one host sync."""
-    dev = inputs_embeds.device
-    B = inputs_embeds.shape[0]
+    select = _sampler(model, inputs_embeds.shape[0], inputs_embeds.device, temperature, top_k, top_p, generator)
+    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, prefill_chunk)
+
+
+def _sampler(model, B, dev, temperature, top_k, top_p, generator):
+    """sample()'s select: one torch.rand(B) and one kernels.sample_top_k_top_p launch per step."""
     V = _stack(model).lm_head.shape[0]
     if V > K.sample_max_vocab():
         raise ValueError("generate: sampling takes a vocabulary of at most %d entries, the head has %d" % (K.sample_max_vocab(), V))
@@ -205,4 +309,92 @@ def sample(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, temperat
         u = torch.rand(B, device=dev, generator=generator)
         tok = K.sample_top_k_top_p(logits, u, temperature, top_k, top_p)
         return tok, tok < 0
-    return _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)
+    return select
+
+
+# ------------------------------------------------------------------------------------------------
+class DecodeSession:
+    """A KV cache kept alive between calls (LlavaLlamaForCausalLM.start_session / VilaLlavaLlamaModel.start_session): generate() continues
+    from the kept last-row logits, append() pushes a text-only next turn through ONE extend() call.
+
+    Per row the session keeps on the host: lens[b], the rows the cache holds, and pending[b], the tokens of the row's history that the
+    cache does not hold yet - generate()'s loop ends without pushing its last selected token through the model.  A row that stopped (EOS, a
+    stopping criterion) counts its tokens up to and including the one it stopped on; the pad tokens behind it belong to no history and are
+    never kept: the loop's decode_step writes them behind the row's last real slot, and lens is set back to the host's count afterwards
+    (slots at or beyond lens[b] are never read)."""
+
+    def __init__(self, model, cache, logits, lens, config=None):
+        self.model, self.cache, self.logits, self.config = model, cache, logits, config
+        self.lens = [int(v) for v in lens]
+        self.pending = [[] for _ in self.lens]
+        self.max_len = cache.Lcap
+
+    def _set_lens(self):
+        cache = self.cache
+        cache.lens.copy_(torch.tensor(self.lens, dtype=torch.int32).to(cache.lens.device).expand_as(cache.lens))
+        cache.filled = max(self.lens)
+
+    def _push(self, new):
+        """pending[b] + new[b] of every row through one extend() call; the logits of a row's last new row replace its kept ones."""
+        rows = [p + list(t) for p, t in zip(self.pending, new)]
+        n_new = [len(r) for r in rows]
+        n = max(n_new)
+        if n == 0:
+            return
+        if max(self.lens) + n > self.max_len:
+            raise RuntimeError("session full: %d rows held, %d more asked for, max_len=%d" % (max(self.lens), n, self.max_len))
+        lm = _stack(self.model).lm
+        dev = lm.embed_tokens.weight.device
+        ids = torch.zeros(len(rows), n, dtype=torch.long)
+        for b, r in enumerate(rows):
+            ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.long)
+        lg = extend(self.model, self.cache, lm.embed_tokens(ids.to(dev)), n_new)
+        live = torch.tensor([v > 0 for v in n_new], device=lg.device)
+        self.logits = torch.where(live[:, None], lg, self.logits)
+        self.lens = [a + b for a, b in zip(self.lens, n_new)]
+        self.pending = [[] for _ in rows]
+        self.cache.filled = max(self.lens)
+
+    @torch.no_grad()
+    def append(self, input_ids, attention_mask=None, images=None):
+        """The next turn, text only: input_ids [B, m] right padded (attention_mask marks each row's ids).  Each row's pending tokens and
+        then its new ids go through one extend() call, ragged.  Exceeding max_len raises RuntimeError before any launch."""
+        if images is not None:
+            raise NotImplementedError("session.append: images in a later turn are not implemented; start a new session")
+        ids = torch.as_tensor(input_ids).detach().cpu().long()
+        if ids.ndim != 2 or ids.shape[0] != len(self.lens):
+            raise ValueError("session.append needs input_ids [B=%d, m]" % len(self.lens))
+        if (ids < 0).any():
+            raise NotImplementedError("session.append: image tokens in a later turn are not implemented")
+        if attention_mask is None:
+            new = [row.tolist() for row in ids]
+        else:
+            mask = torch.as_tensor(attention_mask).detach().cpu().bool()
+            cnt = mask.sum(1).tolist()
+            if any(not bool(mask[b, :c].all()) for b, c in enumerate(cnt)):
+                raise NotImplementedError("session.append: left-padded or gapped rows are not supported; pad on the right")
+            new = [ids[b, :c].tolist() for b, c in enumerate(cnt)]
+        self._push(new)
+
+    @torch.no_grad()
+    def generate(self, max_new_tokens, do_sample=False, temperature=None, top_k=None, top_p=None, eos_token_id=None, pad_token_id=None,
+                 stopping_criteria=None, generator=None):
+        """_generate_loop's rules on the kept cache -> LongTensor [B, n] of the new tokens only (both model families).  Tokens a previous
+        generate() left pending are pushed first."""
+        sampling = check_generate_args(1, do_sample, max_new_tokens, temperature, top_k, top_p)
+        if max(self.lens) + max(len(p) for p in self.pending) + max_new_tokens - 1 > self.max_len:
+            raise RuntimeError("session full: %d rows held, max_new_tokens=%d, max_len=%d" % (max(self.lens), max_new_tokens, self.max_len))
+        self._push([[] for _ in self.lens])
+        dev = self.logits.device
+        B = len(self.lens)
+        eos_ids, pad = eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
+        select = _argmax if sampling is None else _sampler(self.model, B, dev, *sampling, generator)
+        out, real = _loop_from(self.model, self.cache, self.logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, None)
+        toks, real = out.tolist(), real.tolist()
+        pushed = out.shape[1] - 1                       # every column but the last went through decode_step
+        for b in range(B):
+            held = min(real[b], pushed)
+            self.lens[b] += held
+            self.pending[b] = toks[b][held:real[b]]
+        self._set_lens()
+        return out

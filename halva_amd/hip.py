@@ -64,6 +64,9 @@ SIGNATURES = {
     "halva_decode_attn": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
     "halva_decode_attn_kc": [],
     "halva_decode_attn_chunked": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
+    "halva_extend_rope_append": [_P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "halva_extend_attn": [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    "halva_extend_advance": [_P, _P, _I, _I, _P],
     "halva_sample_top_k_top_p": [_P, _L, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P],
     "halva_sample_max_vocab": [],
 }
@@ -107,6 +110,8 @@ def load():
     lib.halva_sdpa_bwd_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
     lib.halva_decode_attn_ws_bytes.restype = c_int64
     lib.halva_decode_attn_ws_bytes.argtypes = [c_int, c_int, c_int]
+    lib.halva_extend_attn_ws_bytes.restype = c_int64
+    lib.halva_extend_attn_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
     _lib = lib
     return lib
 

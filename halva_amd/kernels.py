@@ -313,6 +313,44 @@ def decode_attention(q, kcache, vcache, lens, ws, H, D, out_width=None, ldq=None
     return out
 
 
+def extend_ws_bytes(B, n, H, Lcap):
+    """Workspace bytes of extend_attention (0: one workgroup owns a row from its first key to its last)."""
+    return int(hip.load().halva_extend_attn_ws_bytes(B, n, H, Lcap))
+
+
+def extend_rope_append(qkv, cos, sin, kcache, vcache, lens, n_new, H, D):
+    """qkv [B, n, 3*H*D] (new rows): for i < n_new[b], q of row i rotated in place at position lens[b] + i, rotated k / plain v written to
+    slot lens[b] + i of the [B, H, Lcap, D] caches; lens is NOT advanced (halva_extend_rope_append)."""
+    _chk(qkv, torch.bfloat16, "qkv"), _chk(kcache, torch.bfloat16, "kcache"), _chk(vcache, torch.bfloat16, "vcache")
+    _chk(lens, torch.int32, "lens"), _chk(n_new, torch.int32, "n_new")
+    B, n, ld = qkv.shape
+    call("halva_extend_rope_append", ptr(qkv), ld, n * ld, ptr(cos), ptr(sin), cos.shape[0], ptr(kcache), ptr(vcache), ptr(lens), ptr(n_new),
+         B, n, H, D, kcache.shape[2], stream_ptr())
+    return qkv
+
+
+def extend_attention(q, kcache, vcache, lens, n_new, ws, H, D, out_width=None, out=None):
+    """Rows i < n_new[b] of q [B, n, ldq] (the first H*D columns: the rotated q third of the qkv rows) attend cache slots
+    [0, lens[b] + i] -> bf16 [B, n, out_width] (left H*D columns of those rows written, everything else of a fresh `out` is zero).  Runs
+    behind extend_rope_append and before extend_advance (halva_extend_attn)."""
+    _chk(q, torch.bfloat16, "q"), _chk(kcache, torch.bfloat16, "kcache"), _chk(vcache, torch.bfloat16, "vcache")
+    _chk(lens, torch.int32, "lens"), _chk(n_new, torch.int32, "n_new")
+    B, n, ldq = q.shape
+    width = out_width or H * D
+    if out is None:
+        out = torch.zeros(B, n, width, dtype=torch.bfloat16, device=q.device)
+    call("halva_extend_attn", ptr(q), ldq, n * ldq, ptr(kcache), ptr(vcache), ptr(lens), ptr(n_new), ptr(out), width, n * width,
+         ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), B, n, H, D, kcache.shape[2], 0.0, stream_ptr())
+    return out
+
+
+def extend_advance(lens, n_new, Lcap):
+    """lens[b] = min(lens[b] + n_new[b], Lcap) (halva_extend_advance)."""
+    _chk(lens, torch.int32, "lens"), _chk(n_new, torch.int32, "n_new")
+    call("halva_extend_advance", ptr(lens), ptr(n_new), lens.shape[0], Lcap, stream_ptr())
+    return lens
+
+
 def sample_max_vocab():
     """The widest row sample_top_k_top_p takes (a library constant)."""
     return int(hip.load().halva_sample_max_vocab())

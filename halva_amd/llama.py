@@ -446,6 +446,25 @@ class DecoderLayer(nn.Module):
         act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
         return self.down(act, x, use_lora, mine)
 
+    def extend(self, x, cache, layer_idx, n_new_d, use_lora=True, rows=None):
+        """Up to n new rows per sequence against the KV cache (halva_amd/decode.py:extend), no autograd: decode()'s body on x [B, n, d] (a
+        buffer of the caller's own) -> [B, n, d], with RoPE + append of rows i < n_new_d[b], their attention over the cache and the advance
+        of lens as three launches.  Rows i >= n_new_d[b] carry values nobody reads (every other piece is row-wise).
+        rows: as in forward() - the top layer runs its row-wise part on those flat rows of [B * n] only and returns [len(rows), d]."""
+        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, True)
+        qkv = self.qkv(h, None, use_lora)
+        kc, vc = cache.k[layer_idx], cache.v[layer_idx]
+        lens = cache.lens[layer_idx]
+        K.extend_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, n_new_d, self.H, self.D)
+        a = K.extend_attention(qkv, kc, vc, lens, n_new_d, cache.extend_ws(qkv.shape[1]), self.H, self.D, self.o.in_width)
+        K.extend_advance(lens, n_new_d, cache.Lcap)
+        if rows is not None:
+            a, x, mine = _take_rows(a, rows), _take_rows(x, rows), RES_INPLACE
+        x = self.o(a, x, use_lora, mine)
+        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)
+        act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
+        return self.down(act, x, use_lora, mine)
+
 
 class LlamaModel(nn.Module):
     def __init__(self, cfg, dtype=torch.bfloat16, device="cuda"):

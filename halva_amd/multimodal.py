@@ -184,13 +184,9 @@ class MultimodalMixin:
         from .decode import DecodeStack
         return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
 
-    @torch.no_grad()
-    def _generate(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None):
-        """The body of `generate`: the prompt is spliced when there are images, a tower and more than one token, else embedded;
-        then halva_amd/decode.py:greedy, or :sample when do_sample is set.  Right padding only."""
-        from . import decode as DEC
-        sampling = DEC.check_generate_args(num_beams, do_sample, max_new_tokens, temperature, top_k, top_p)
+    def _embed_prompt(self, input_ids, images, attention_mask):
+        """The front part of generation: the prompt spliced when there are images, a tower and more than one token, else embedded.
+        Right padding only.  -> (inputs_embeds [B, T, d], seq_len int32 [B] on the host)."""
         if input_ids is None or input_ids.ndim != 2:
             raise ValueError("generate needs input_ids [B, T]")
         dev = self.device
@@ -216,11 +212,48 @@ class MultimodalMixin:
                 seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
         if int(seq_start.max()) != 0:
             raise NotImplementedError(_LEFT_PADDED)
+        return embeds, seq_len
+
+    @torch.no_grad()
+    def _generate(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
+                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None, prefill_chunk=None):
+        """The body of `generate`: _embed_prompt, then halva_amd/decode.py:greedy, or :sample when do_sample is set.  prefill_chunk: None =
+        one prompt pass; an int >= 1 = the prompt pass in blocks of that many rows (decode.prefill_chunked)."""
+        from . import decode as DEC
+        sampling = DEC.check_generate_args(num_beams, do_sample, max_new_tokens, temperature, top_k, top_p)
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("generate: prefill_chunk=%r (needs an int >= 1, or None)" % (prefill_chunk,))
+        embeds, seq_len = self._embed_prompt(input_ids, images, attention_mask)
+        dev = self.device
         eos_ids, pad = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, dev)
         prompt = input_ids.to(dev) if self.generate_returns_prompt else None
         if sampling is None:
-            out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt)
+            out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
         else:
             out = DEC.sample(self, embeds, seq_len, max_new_tokens, eos_ids, pad, *sampling, generator=generator,
-                             stopping_criteria=stopping_criteria, prefix=prompt)
+                             stopping_criteria=stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
         return out if prompt is None else torch.cat([prompt.long(), out], 1)
+
+    @torch.no_grad()
+    def start_session(self, input_ids, images=None, attention_mask=None, max_len=None, prefill_chunk=None):
+        """A decoding session that keeps its KV cache between calls (halva_amd/decode.py:DecodeSession): the prompt is spliced and embedded
+        exactly as generate() does, a cache of max_len slots (default: tokenizer_model_max_length, else the prompt's rows + 256) is
+        allocated and prefilled (in blocks of prefill_chunk rows when given), and the last-row logits are kept.  Then
+        session.generate(max_new_tokens, ...) -> the new tokens [B, n], session.append(input_ids, attention_mask) for a text-only next
+        turn; session.lens is the host list of rows held per sequence."""
+        from . import decode as DEC
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("start_session: prefill_chunk=%r (needs an int >= 1, or None)" % (prefill_chunk,))
+        embeds, seq_len = self._embed_prompt(input_ids, images, attention_mask)
+        T = embeds.shape[1]
+        if max_len is None:
+            max_len = max(getattr(self._lm_config(), "tokenizer_model_max_length", None) or 0, T + 256)
+        if int(max_len) < T:
+            raise ValueError("start_session: max_len=%d is below the prompt's %d rows" % (max_len, T))
+        cache = DEC.KVCache(self, embeds.shape[0], int(max_len), embeds.device)
+        if prefill_chunk is None:
+            logits = DEC.prefill(self, embeds, seq_len, cache)
+        else:
+            logits = DEC.prefill_chunked(self, embeds, seq_len, cache, prefill_chunk)
+        cache.filled = int(seq_len.max())
+        return DEC.DecodeSession(self, cache, logits, seq_len.tolist(), self._lm_config())

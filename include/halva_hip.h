@@ -316,6 +316,34 @@ int64_t halva_decode_attn_ws_bytes(int B, int H, int Lcap);
 int halva_decode_attn_chunked(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* lens, void* out,
                               int64_t ld_out, void* ws, int64_t ws_bytes, int B, int H, int D, int Lcap, float scale, int kc, void* stream);
 
+/* ---- Extending a kept cache by up to n rows per sequence (halva_amd/decode.py:extend - sessions, chunked prefill, block teacher forcing).
+ * stands in for the reference's multi-turn use of HF's cache: a forward with past_key_values and q_len = n (modelling_llama.py:295-340, the
+ * cache concat and the [q_len, past + q_len] causal mask).  Same cache layout, D = 128; lens int32 [B] (past[b] = lens[b]) and n_new int32 [B]
+ * (0 <= n_new[b] <= n) live on the device, no launch takes a host-side length.  Three launches in this order; the first two only read lens,
+ * so no workgroup reads a lens value written by its own launch.
+ *
+ * RoPE + append.  qkv: bf16 [B, n, 3, H, D], row i of sequence b at qkv[b * ldseq + i * ldrow].  For i < n_new[b], p = lens[b] + i: q and k of
+ * the row rotated with row p of cos / sin (halva_decode_rope_append's arithmetic, bitwise), q in place, the rotated k and the plain v written
+ * to slot p.  Rows i >= n_new[b] are neither read nor written; a row with p >= min(Lcap, max_pos) is skipped (the caller refuses such calls;
+ * nothing is written out of bounds).  One workgroup per (row, sequence). */
+int halva_extend_rope_append(void* qkv, int64_t ldrow, int64_t ldseq, const void* cos, const void* sin, int max_pos, void* kcache, void* vcache,
+                             const int32_t* lens, const int32_t* n_new, int B, int n, int H, int D, int Lcap, void* stream);
+/* Attention of the new rows, after the append and before the advance:
+ *   out[b, i, h, :] = softmax(scale q[b, i, h] . K[b, h, 0 .. past[b] + i]) V[b, h, 0 .. past[b] + i]      for i < n_new[b]
+ * (key past + j is visible to row i iff j <= i); other out rows are untouched.  q: row at q[b * ldseq + i * ldrow + h * D] (the rotated q third of
+ * the qkv rows), out: bf16 row at out[b * ld_out_seq + i * ld_out_row + h * D].  One workgroup of 4 waves per (128 query rows, head, sequence)
+ * walks the keys from 0 in 64-key LDS tiles: Q K^T and P V on v_mfma_f32_32x32x16_bf16 (V read transposed by ds_read_b64_tr_b16), fp32 online
+ * softmax in the log2 domain whose exponent reference starts at the first tile (it always holds key 0: finite for any real logits) and moves
+ * per row.  One reduction order fixed by (past[b], i) alone, no float atomics: row (b, i) is bitwise the same at any B and any n_new of the
+ * other sequences.  Slots at or beyond past[b] + n_new[b] and q rows at or beyond n_new[b] are never read.  scale = 1/sqrt(D) when <= 0.
+ * ws_bytes >= halva_extend_attn_ws_bytes(B, n, H, Lcap), which is 0 (no partials; ws may be NULL). */
+int halva_extend_attn(const void* q, int64_t ldrow, int64_t ldseq, const void* kcache, const void* vcache, const int32_t* lens,
+                      const int32_t* n_new, void* out, int64_t ld_out_row, int64_t ld_out_seq, void* ws, int64_t ws_bytes, int B, int n, int H,
+                      int D, int Lcap, float scale, void* stream);
+int64_t halva_extend_attn_ws_bytes(int B, int n, int H, int Lcap);
+/* lens[b] = min(lens[b] + n_new[b], Lcap): a launch of its own behind the attention. */
+int halva_extend_advance(int32_t* lens, const int32_t* n_new, int B, int Lcap, void* stream);
+
 /* ---- Sampling (generate with do_sample=True, halva_amd/decode.py:sample).  replaces what HF's generate runs per step behind the reference's
  * `model.generate(..., do_sample=True, temperature=args.temperature, top_p=args.top_p, ...)` (eval_hall/model_chair_loader.py:124-130):
  * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper(min_tokens_to_keep=1) -> softmax -> torch.multinomial, i.e. about ten

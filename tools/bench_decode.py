@@ -15,7 +15,12 @@ the same decode steps are timed again; the record gains `merged` = {merge_s, wei
 and of the torch composition it stands in for (softmax, sort, cumsum, scatter, softmax, multinomial, as HF's warpers run them) on the same
 logits, and ms per step of the whole sampled loop (decode.sample) beside the greedy loop (decode.greedy) on the same prompts.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--out profiles/r07_decode.json] [--steps 32]
+--extend: the record gains `extend` (7B geometry, H = 32, B = 1 and 16): us per call of the extend attention (halva_extend_attn) at
+past = 0, n = 639 beside halva_sdpa_causal_fwd_ld on the same rows (the prompt pass's attention), of the extend attention at past = 639,
+n = 32, and - with the model - ms of a second turn of 32 ids through session.append beside a fresh start_session (vision tower, splice,
+prompt pass) on the concatenated prompt.  Measurement only, no gate.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -192,6 +197,60 @@ def loop_numbers(m, steps, text=64, image=336):
     return {"temperature": T_, "top_k": k, "top_p": p, "loop": res}
 
 
+def extend_kernel_numbers(H=32, D=128, T=639, n2=32, reps=20):
+    from halva_amd import hip
+    from halva_amd import kernels as K
+    dev = "cuda"
+    res = {}
+    for B in (1, 16):
+        L = T + n2
+        qkv = torch.randn(B, T, 3 * H * D, device=dev).to(torch.bfloat16)
+        kc = torch.randn(B, H, L, D, device=dev).to(torch.bfloat16)
+        vc = torch.randn(B, H, L, D, device=dev).to(torch.bfloat16)
+        zero = torch.zeros(B, dtype=torch.int32, device=dev)
+        full = torch.full((B,), T, dtype=torch.int32, device=dev)
+        out = torch.empty(B, T, H * D, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B, H, T, dtype=torch.float32, device=dev)
+        ext0 = _time(lambda: K.extend_attention(qkv, kc, vc, zero, full, None, H, D, out=out), reps, warmup=3)
+        sdpa = _time(lambda: hip.call("halva_sdpa_causal_fwd_ld", hip.ptr(qkv), hip.ptr(out), H * D, hip.ptr(lse), hip.ptr(zero), hip.ptr(full),
+                                      B, T, H, D, 0.0, hip.stream_ptr()), reps, warmup=3)
+        q2 = qkv[:, :n2].contiguous()
+        out2 = torch.empty(B, n2, H * D, dtype=torch.bfloat16, device=dev)
+        few = torch.full((B,), n2, dtype=torch.int32, device=dev)
+        ext1 = _time(lambda: K.extend_attention(q2, kc, vc, full, few, None, H, D, out=out2), reps, warmup=3)
+        res["B%d" % B] = {"extend_past0_n%d_us" % T: round(ext0 * 1e3, 1), "sdpa_causal_fwd_T%d_us" % T: round(sdpa * 1e3, 1),
+                          "extend_past%d_n%d_us" % (T, n2): round(ext1 * 1e3, 1)}
+    return res
+
+
+def extend_turn_numbers(m, text=64, image=336, turn=32):
+    g = torch.Generator().manual_seed(0)
+    res = {}
+    for B in (1, 16):
+        ids = torch.randint(3, 32000, (B, text), generator=g)
+        ids[:, 0] = 1
+        ids[:, 6] = -200
+        more = torch.randint(3, 32000, (B, turn), generator=g)
+        images = torch.randn(B, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+        state = {}
+
+        def first():
+            state["ses"] = m.start_session(ids, images=images, max_len=2 * (text + turn) + 1024)
+
+        def second():
+            ses = state["ses"]
+            ses.lens = list(state["lens"])          # every timed pass appends at the same position
+            ses._set_lens()
+            ses.append(more)
+        first()
+        state["lens"] = list(state["ses"].lens)
+        app_ms = _time(second, 3, warmup=1)
+        both = torch.cat([ids, more], 1)
+        fresh_ms = _time(lambda: m.start_session(both, images=images, max_len=2 * (text + turn) + 1024), 3, warmup=1)
+        res["B%d" % B] = {"prompt_rows": state["lens"][0], "turn_ids": turn, "append_ms": round(app_ms, 2), "fresh_prefill_ms": round(fresh_ms, 2)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -200,6 +259,7 @@ def main():
     ap.add_argument("--model", choices=("llava7b", "vila13b"), default="llava7b")
     ap.add_argument("--merged", action="store_true", help="also time the decode step after merge_and_unload() on the same model")
     ap.add_argument("--sample", action="store_true", help="also time the native token select, its torch composition and the sampled loop")
+    ap.add_argument("--extend", action="store_true", help="also time the extend attention beside the prompt pass's, and a session's second turn")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
@@ -209,6 +269,8 @@ def main():
            "decode_attn": attn_kernel(H=40, L=4096) if vila else attn_kernel()}
     if a.sample:
         rec["sample"] = select_numbers()
+    if a.extend:
+        rec["extend"] = extend_kernel_numbers()
     if not a.skip_model:
         m = model_vila13b() if vila else model_7b()
         def weights_gb():
@@ -220,6 +282,8 @@ def main():
         rec["decode"] = numbers()
         if a.sample:
             rec["sample"].update(loop_numbers(m, a.steps, text=60, image=384) if vila else loop_numbers(m, a.steps))
+        if a.extend:
+            rec["extend"]["second_turn"] = extend_turn_numbers(m, text=60, image=384) if vila else extend_turn_numbers(m)
         if a.merged:
             import time
             torch.cuda.synchronize()
