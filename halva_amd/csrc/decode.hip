@@ -1,71 +1,32 @@
 // Single-token decode over a KV cache (greedy generation, halva_amd/decode.py) on gfx950: RoPE + cache append of the new token, and
 // split-KV ("flash-decoding") attention of one query row per (sequence, head).  Both are HBM-bound and use no MFMA: M = 1 per head.
+// The rotation and the cache write of a row are rope_append.h's one routine, which extend.hip calls for its rows too.
 //
 // Cache layout, per layer: K, V bf16 [B, H, Lcap, 128]; lens int32 [B] on the device (never a launch-time host value, so the step can
 // be captured in a graph later).  Slots at or beyond lens[b] are never read.
 #include "common.h"
+#include "rope_append.h"
 #include <cmath>
 
 namespace {
 
 constexpr int kDecD = 128;          // head_dim of the LLaVA-1.5 decoder
 constexpr int kDecChunks = kDecD / 8;      // 16-byte pieces per head row
+static_assert(kDecChunks == kRopeChunks, "rope_append_row serves this head_dim");
 constexpr int kDecWaves = 4;        // waves per split-KV workgroup
-
-__device__ __forceinline__ void dec_unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf16_lo(v[i]);
-        f[2 * i + 1] = bf16_hi(v[i]);
-    }
-}
-__device__ __forceinline__ u32x4 dec_pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // RoPE of the new token + cache append.  One workgroup per sequence b: every thread reads lens[b] before the barrier, thread 0 advances
-// it after, so no other reader of this launch sees the new value.  qkv row b = [3, H, D]; q rotated in place (rope_qk_kernel's arithmetic),
-// rotated k and plain v written to slot lens[b].
+// it after, so no other reader of this launch sees the new value.  qkv row b = [3, H, D] goes through rope_append_row (rope_append.h, shared
+// with extend.hip) at position lens[b].
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void decode_rope_append_kernel(u32x4* __restrict__ qkv, int64_t ldq_chunks, const u32x4* __restrict__ cosb,
                                                                  const u32x4* __restrict__ sinb, int max_pos, u32x4* __restrict__ kc,
                                                                  u32x4* __restrict__ vc, int32_t* __restrict__ lens, int H, int Lcap) {
-    constexpr int CH = kDecChunks / 2;          // 16-byte pieces per half head row
     const int b = blockIdx.x;
     const int p = lens[b];
     const bool ok = p >= 0 && p < Lcap && p < max_pos;      // (the host sizes the cache; a full one is left untouched, never overrun)
-    u32x4* row = qkv + (int64_t)b * ldq_chunks;
-    if (ok) {
-        for (int i = threadIdx.x; i < 2 * H * CH; i += blockDim.x) {
-            const int c = i % CH;
-            const int h = (i / CH) % H;
-            const int part = i / (CH * H);      // 0 = q, 1 = k
-            const int64_t base = (int64_t)(part * H + h) * kDecChunks + c;
-            float x1[8], x2[8], cs[8], sn[8], y1[8], y2[8];
-            dec_unpack8(row[base], x1);
-            dec_unpack8(row[base + CH], x2);
-            dec_unpack8(cosb[(int64_t)p * CH + c], cs);
-            dec_unpack8(sinb[(int64_t)p * CH + c], sn);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) rope_pair(x1[j], x2[j], cs[j], sn[j], y1[j], y2[j]);
-            if (part == 0) {
-                row[base] = dec_pack8(y1);
-                row[base + CH] = dec_pack8(y2);
-            } else {
-                u32x4* dst = kc + (((int64_t)b * H + h) * Lcap + p) * kDecChunks + c;
-                dst[0] = dec_pack8(y1);
-                dst[CH] = dec_pack8(y2);
-            }
-        }
-        for (int i = threadIdx.x; i < H * kDecChunks; i += blockDim.x) {
-            const int h = i / kDecChunks, c = i % kDecChunks;
-            vc[(((int64_t)b * H + h) * Lcap + p) * kDecChunks + c] = row[(int64_t)(2 * H + h) * kDecChunks + c];
-        }
-    }
+    if (ok) rope_append_row(qkv + (int64_t)b * ldq_chunks, cosb, sinb, kc, vc, b, p, H, Lcap);
     __syncthreads();
     if (threadIdx.x == 0 && ok) lens[b] = p + 1;
 }
@@ -91,7 +52,7 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const u32x4* _
     const int sub = lane & 15, grp = lane >> 4;
     const int64_t bh = (int64_t)b * H + h;
     float qf[8];
-    dec_unpack8(q[(int64_t)b * ldq_chunks + h * kDecChunks + sub], qf);
+    unpack8(q[(int64_t)b * ldq_chunks + h * kDecChunks + sub], qf);
 #pragma unroll
     for (int j = 0; j < 8; ++j) qf[j] *= qscale;
     const u32x4* kb = kc + bh * Lcap * kDecChunks + sub;
@@ -113,7 +74,7 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const u32x4* _
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         float f[8];
-        dec_unpack8(kr[i], f);
+        unpack8(kr[i], f);
         float d = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) d = fmaf(qf[j], f[j], d);
@@ -132,7 +93,7 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const u32x4* _
         for (int i = 0; i < NI; ++i) {
             const float p = exp2f(s[i] - m);
             float f[8];
-            dec_unpack8(vr[i], f);
+            unpack8(vr[i], f);
             l += p;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = fmaf(p, f[j], o[j]);

@@ -1,10 +1,12 @@
 // Extending a kept KV cache by a block of rows (halva_amd/decode.py:extend - sessions, chunked prefill, block teacher forcing) on gfx950:
 // RoPE + cache append of up to n new rows per sequence, causal attention of those rows over the past + n keys of the cache on MFMA, and the
-// launch that advances lens.  Three launches, so that no workgroup ever reads a lens value written by its own launch.
+// launch that advances lens.  Three launches, so that no workgroup ever reads a lens value written by its own launch.  The rotation and the
+// cache write of a row are rope_append.h's one routine, the one decode.hip's append calls: the two cannot differ in arithmetic.
 //
 // Cache layout as decode.hip: K, V bf16 [B, H, Lcap, 128]; lens int32 [B] and n_new int32 [B] on the device (never a launch-time host
 // value).  With past = lens[b]: slots at or beyond past + n_new[b] and q rows at or beyond n_new[b] are never read.
 #include "common.h"
+#include "rope_append.h"
 #include <cmath>
 
 namespace {
@@ -12,70 +14,30 @@ namespace {
 #include "sdpa_common.h"      // tile_off / mfma32 / frag_rows / frag_cols / Stage / store_rows_T: the attention kernels' tile pieces
 
 constexpr int kExtD = 128;                // head_dim of the decoder
-constexpr int kExtChunks = kExtD / 8;     // 16-byte pieces per head row
+static_assert(kExtD == 8 * kRopeChunks, "rope_append_row serves this head_dim");
 constexpr int kExtBM = 128;               // query rows per workgroup: 4 waves x 32
 constexpr int kExtBN = 64;                // keys per LDS tile
 constexpr int kExtWaves = kExtBM / 32;
 constexpr int kExtTileBytes = kExtBN * kExtD * 2;
 constexpr float kExtRescaleAt = 64.f;     // log2 units (sdpa_fwd.h: P stays below 2^64)
 
-__device__ __forceinline__ void ext_unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf16_lo(v[i]);
-        f[2 * i + 1] = bf16_hi(v[i]);
-    }
-}
-__device__ __forceinline__ u32x4 ext_pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // how many of the n rows of sequence b are new: n_new[b] cut to [0, n] and to the free slots of the cache
 __device__ __forceinline__ int ext_rows(int past, int nn, int n, int Lcap) { return max(min(min(nn, n), Lcap - past), 0); }
 
 // ---------------------------------------------------------------------------------------------------
-// RoPE + append.  One workgroup per (row i, sequence b), decode_rope_append_kernel's arithmetic on row i at position lens[b] + i.  lens is
-// only read.
+// RoPE + append.  One workgroup per (row i, sequence b): rope_append_row (rope_append.h, the routine decode_rope_append_kernel calls) on
+// row i at position lens[b] + i.  lens is only read.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void extend_rope_append_kernel(u32x4* __restrict__ qkv, int64_t ldrow_chunks, int64_t ldseq_chunks,
                                                                  const u32x4* __restrict__ cosb, const u32x4* __restrict__ sinb, int max_pos,
                                                                  u32x4* __restrict__ kc, u32x4* __restrict__ vc, const int32_t* __restrict__ lens,
                                                                  const int32_t* __restrict__ n_new, int n, int H, int Lcap) {
-    constexpr int CH = kExtChunks / 2;          // 16-byte pieces per half head row
     const int i = blockIdx.x, b = blockIdx.y;
     const int past = lens[b];
     if (past < 0 || i >= min(n_new[b], n)) return;
     const int p = past + i;
     if (p >= Lcap || p >= max_pos) return;      // (the host refuses such calls; never written out of bounds)
-    u32x4* row = qkv + (int64_t)b * ldseq_chunks + (int64_t)i * ldrow_chunks;
-    for (int t = threadIdx.x; t < 2 * H * CH; t += blockDim.x) {
-        const int c = t % CH;
-        const int h = (t / CH) % H;
-        const int part = t / (CH * H);          // 0 = q, 1 = k
-        const int64_t base = (int64_t)(part * H + h) * kExtChunks + c;
-        float x1[8], x2[8], cs[8], sn[8], y1[8], y2[8];
-        ext_unpack8(row[base], x1);
-        ext_unpack8(row[base + CH], x2);
-        ext_unpack8(cosb[(int64_t)p * CH + c], cs);
-        ext_unpack8(sinb[(int64_t)p * CH + c], sn);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) rope_pair(x1[j], x2[j], cs[j], sn[j], y1[j], y2[j]);
-        if (part == 0) {
-            row[base] = ext_pack8(y1);
-            row[base + CH] = ext_pack8(y2);
-        } else {
-            u32x4* dst = kc + (((int64_t)b * H + h) * Lcap + p) * kExtChunks + c;
-            dst[0] = ext_pack8(y1);
-            dst[CH] = ext_pack8(y2);
-        }
-    }
-    for (int t = threadIdx.x; t < H * kExtChunks; t += blockDim.x) {
-        const int h = t / kExtChunks, c = t % kExtChunks;
-        vc[(((int64_t)b * H + h) * Lcap + p) * kExtChunks + c] = row[(int64_t)(2 * H + h) * kExtChunks + c];
-    }
+    rope_append_row(qkv + (int64_t)b * ldseq_chunks + (int64_t)i * ldrow_chunks, cosb, sinb, kc, vc, b, p, H, Lcap);
 }
 
 __global__ void extend_advance_kernel(int32_t* __restrict__ lens, const int32_t* __restrict__ n_new, int B, int Lcap) {

@@ -18,19 +18,6 @@ constexpr int kMaxChunks = 16;   // 16 chunks x 64 lanes x 8 elements = rows up 
         else { CALL(16); }                 \
     } while (0)
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf16_lo(v[i]);
-        f[2 * i + 1] = bf16_hi(v[i]);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
 // bytes that are read once / written once by a streaming row kernel: nontemporal (they would only push the GEMMs' operands out of the caches)
 __device__ __forceinline__ u32x4 stream_load(const u32x4* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void stream_store(u32x4* p, const u32x4& v) { __builtin_nontemporal_store(v, p); }

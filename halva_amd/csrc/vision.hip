@@ -8,20 +8,6 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 constexpr int kMaxChunks = 16;   // rows up to d = 8192 stay in registers
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = bf16_lo(v[i]);
-        f[2 * i + 1] = bf16_hi(v[i]);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // y = bf16((x - mean) * rstd * w + b), statistics in fp32 over the bf16 row (torch.nn.LayerNorm on bf16 input)
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const u32x4* __restrict__ x, const u32x4* __restrict__ w,
                                                             const u32x4* __restrict__ b, u32x4* __restrict__ y,

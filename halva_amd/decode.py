@@ -49,14 +49,6 @@ class KVCache:
             lm._rope = {}
             cos, sin = lm.rope(Lcap, dev)
         self.cos, self.sin = cos, sin
-        self._ext_ws = None        # the extend attention's workspace: allocated on first use (extend_ws), so a cache that is never extended keeps its size
-
-    def extend_ws(self, n):
-        """The workspace of kernels.extend_attention for blocks of n rows, allocated (or grown) on first use."""
-        need = max(K.extend_ws_bytes(self.B, n, self.H, self.Lcap), 16)
-        if self._ext_ws is None or self._ext_ws.numel() < need:
-            self._ext_ws = torch.empty(need, dtype=torch.uint8, device=self.k[0].device)
-        return self._ext_ws
 
     def fill(self, layer_idx, qkv, seq_len):
         """Prompt pass: the rotated k and the plain v of the [B, T, 3*H*D] projection into slots [0, T) (rows past seq_len[b] are
@@ -103,9 +95,8 @@ def decode_step(model, cache, token_ids):
     st = _stack(model)
     lm = st.lm
     x = lm.embed_tokens(token_ids.to(lm.embed_tokens.weight.device).long())          # a fresh buffer: the residual adds run on it in place
-    for i, layer in enumerate(lm.layers):
-        x = layer.decode(x, cache, i, st.use_lora)
-    return _lm_head(st, lm.norm(x))
+    x = lm.each_layer(x, None, lambda i, layer, x, top: (layer.decode(x, cache, i, st.use_lora), None))
+    return _lm_head(st, x)
 
 
 @torch.no_grad()
@@ -114,7 +105,6 @@ def extend(model, cache, inputs_embeds, n_new):
     0 <= n_new[b] <= n (sequence b pushes its rows [0, n_new[b]) at positions lens[b] ..) -> logits [B, V] fp32 of each sequence's last new
     row.  A sequence with n_new[b] == 0 is left as it is (cache and lens untouched) and gets NaN logits: callers mask them.  Every check
     runs before the first launch; a block that does not fit raises RuntimeError like decode_step's."""
-    from .llama import TOP_ROWS
     st = _stack(model)
     lm = st.lm
     if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != cache.B:
@@ -134,15 +124,7 @@ def extend(model, cache, inputs_embeds, n_new):
     n_new_d = n_new.to(dev)
     rows = (torch.arange(B, dtype=torch.int64) * n + (n_new.long() - 1).clamp_(min=0)).to(dev)
     x = inputs_embeds.to(dev, torch.bfloat16, copy=True).contiguous()      # a buffer of our own: the residual adds run on it in place
-    last = len(lm.layers) - 1
-    for i, layer in enumerate(lm.layers):
-        top = rows if (TOP_ROWS and i == last) else None
-        x = layer.extend(x, cache, i, n_new_d, st.use_lora, top)
-        if top is not None:
-            rows = None
-    x = lm.norm(x)
-    if rows is not None:
-        x = x.view(-1, x.shape[-1]).index_select(0, rows)
+    x = lm.each_layer(x, rows, lambda i, layer, x, top: (layer.extend(x, cache, i, n_new_d, st.use_lora, top), None))
     return _lm_head(st, x).masked_fill_((n_new_d == 0)[:, None], float("nan"))
 
 

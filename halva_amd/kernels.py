@@ -313,11 +313,6 @@ def decode_attention(q, kcache, vcache, lens, ws, H, D, out_width=None, ldq=None
     return out
 
 
-def extend_ws_bytes(B, n, H, Lcap):
-    """Workspace bytes of extend_attention (0: one workgroup owns a row from its first key to its last)."""
-    return int(hip.load().halva_extend_attn_ws_bytes(B, n, H, Lcap))
-
-
 def extend_rope_append(qkv, cos, sin, kcache, vcache, lens, n_new, H, D):
     """qkv [B, n, 3*H*D] (new rows): for i < n_new[b], q of row i rotated in place at position lens[b] + i, rotated k / plain v written to
     slot lens[b] + i of the [B, H, Lcap, D] caches; lens is NOT advanced (halva_extend_rope_append)."""

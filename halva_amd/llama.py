@@ -416,52 +416,49 @@ class DecoderLayer(nn.Module):
         attention is row-wise, so the o projection, the post-attention norm and the MLP run on those rows alone and [n, d] is returned.
         kv_hook: callable(qkv) handed the rotated [S, T, 3*H*D] projection after the attention (the prompt pass of generation fills its
         KV cache from it, halva_amd/decode.py); None on the training path."""
-        # every producer kernel writes straight into the (wider) operand buffer of the projection that follows it
-        # (norm(x), x') come out of one autograd node so that the residual's gradient is added inside the norm's backward kernel, and
-        # x' is a buffer of the block's own: the o / down projections accumulate onto it (no copy of the residual)
-        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, own_x)
-        qkv = self.qkv(h, None, use_lora)
-        a = K.attention(qkv, info.cos, info.sin, info.seq_start, info.seq_len, self.H, self.D, self.o.in_width, info.branch)
-        if kv_hook is not None:
-            kv_hook(qkv)
-        if rows is not None:
-            a, x, mine = _take_rows(a, rows), _take_rows(x, rows), RES_INPLACE      # (the gathered residual is a buffer of this block's own)
-        x = self.o(a, x, use_lora, mine)
-        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)      # (x is this block's own by now)
-        act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
-        return self.down(act, x, use_lora, mine)
+        def attend(qkv):
+            a = K.attention(qkv, info.cos, info.sin, info.seq_start, info.seq_len, self.H, self.D, self.o.in_width, info.branch)
+            if kv_hook is not None:
+                kv_hook(qkv)
+            return a
+        return self._block(x, attend, use_lora, own_x, rows)
 
     def decode(self, x, cache, layer_idx, use_lora=True):
         """One new token per sequence against the KV cache (halva_amd/decode.py), no autograd: x [B, d] (a buffer of the caller's own:
         the residual adds accumulate onto it) -> [B, d].  The same pieces as forward() - the norms, the LoRA groups with their factors
         applied unmerged, SwiGLU - with the attention replaced by RoPE + cache append and the split-KV decode kernel."""
-        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, True)
-        qkv = self.qkv(h, None, use_lora)
-        kc, vc = cache.k[layer_idx], cache.v[layer_idx]
-        lens = cache.lens[layer_idx]
-        K.decode_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, self.H, self.D)
-        a = K.decode_attention(qkv, kc, vc, lens, cache.ws, self.H, self.D, self.o.in_width)
-        x = self.o(a, x, use_lora, mine)
-        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)
-        act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
-        return self.down(act, x, use_lora, mine)
+        kc, vc, lens = cache.k[layer_idx], cache.v[layer_idx], cache.lens[layer_idx]
+
+        def attend(qkv):
+            K.decode_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, self.H, self.D)
+            return K.decode_attention(qkv, kc, vc, lens, cache.ws, self.H, self.D, self.o.in_width)
+        return self._block(x, attend, use_lora, True, None)
 
     def extend(self, x, cache, layer_idx, n_new_d, use_lora=True, rows=None):
         """Up to n new rows per sequence against the KV cache (halva_amd/decode.py:extend), no autograd: decode()'s body on x [B, n, d] (a
         buffer of the caller's own) -> [B, n, d], with RoPE + append of rows i < n_new_d[b], their attention over the cache and the advance
         of lens as three launches.  Rows i >= n_new_d[b] carry values nobody reads (every other piece is row-wise).
         rows: as in forward() - the top layer runs its row-wise part on those flat rows of [B * n] only and returns [len(rows), d]."""
-        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, True)
-        qkv = self.qkv(h, None, use_lora)
-        kc, vc = cache.k[layer_idx], cache.v[layer_idx]
-        lens = cache.lens[layer_idx]
-        K.extend_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, n_new_d, self.H, self.D)
-        a = K.extend_attention(qkv, kc, vc, lens, n_new_d, cache.extend_ws(qkv.shape[1]), self.H, self.D, self.o.in_width)
-        K.extend_advance(lens, n_new_d, cache.Lcap)
+        kc, vc, lens = cache.k[layer_idx], cache.v[layer_idx], cache.lens[layer_idx]
+
+        def attend(qkv):
+            K.extend_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, n_new_d, self.H, self.D)
+            a = K.extend_attention(qkv, kc, vc, lens, n_new_d, None, self.H, self.D, self.o.in_width)      # (its workspace is empty by design)
+            K.extend_advance(lens, n_new_d, cache.Lcap)
+            return a
+        return self._block(x, attend, use_lora, True, rows)
+
+    def _block(self, x, attend, use_lora, own_x, rows):
+        """The decoder block, written once for forward(), decode() and extend(): attend(qkv) -> a [.., o.in_width] is all that differs."""
+        # every producer kernel writes straight into the (wider) operand buffer of the projection that follows it
+        # (norm(x), x') come out of one autograd node so that the residual's gradient is added inside the norm's backward kernel, and
+        # x' is a buffer of the block's own: the o / down projections accumulate onto it (no copy of the residual)
+        h, x, mine = self.input_layernorm.fork(x, self.qkv.in_width, own_x)
+        a = attend(self.qkv(h, None, use_lora))
         if rows is not None:
-            a, x, mine = _take_rows(a, rows), _take_rows(x, rows), RES_INPLACE
+            a, x, mine = _take_rows(a, rows), _take_rows(x, rows), RES_INPLACE      # (the gathered residual is a buffer of this block's own)
         x = self.o(a, x, use_lora, mine)
-        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)
+        h, x, mine = self.post_attention_layernorm.fork(x, self.gate_up.in_width, True)      # (x is this block's own by now)
         act = K.swiglu(self.gate_up(h, None, use_lora), self.down.in_width)
         return self.down(act, x, use_lora, mine)
 
@@ -516,34 +513,32 @@ class LlamaModel(nn.Module):
             self._rope = {}
             cos, sin = self.rope(T, x.device)
         info = SeqInfo(cos, sin, seq_start, seq_len, branch)
-        if kv_hook is not None:
-            return self._prefill_layers(x, info, use_lora, rows, kv_hook)
+        if kv_hook is not None and torch.is_grad_enabled():
+            raise RuntimeError("the prompt pass of generation runs under torch.no_grad()")
         hook = self.grad_ready_hook if torch.is_grad_enabled() else None
-        for i, layer in enumerate(self.layers):
+
+        def step(i, layer, x, top):
             if hook is not None and x.requires_grad:
                 # the gradient of layer i's input is the last thing layer i's backward produces: every kernel that adds into
                 # the LoRA gradient segments of layers >= i has been enqueued when this fires
-                x.register_hook(lambda g, i=i, hook=hook: hook(i))
+                x.register_hook(lambda g: hook(i))
             if self.gradient_checkpointing and torch.is_grad_enabled() and x.requires_grad:
-                x = torch.utils.checkpoint.checkpoint(layer, x, info, use_lora, use_reentrant=False)
-            elif rows is not None and TOP_ROWS and i == len(self.layers) - 1:
-                x = layer(x, info, use_lora, i > 0, rows)
-                rows = None
-            else:
-                x = layer(x, info, use_lora, i > 0)      # from layer 1 on `x` is the previous layer's own output
-        x = self.norm(x)
-        return x if rows is None else x.view(-1, x.shape[-1]).index_select(0, rows)
+                return torch.utils.checkpoint.checkpoint(layer, x, info, use_lora, use_reentrant=False), top      # (every row: `top` goes back)
+            fill = () if kv_hook is None else (lambda qkv: kv_hook(i, qkv),)      # (BaseOnlyLayer.forward has no kv_hook parameter)
+            return layer(x, info, use_lora, i > 0, top, *fill), None      # from layer 1 on `x` is the previous layer's own output
+        return self.each_layer(x, rows, step)
 
-    def _prefill_layers(self, x, info, use_lora, rows, kv_hook):
-        """run_layers' loop for the prompt pass of generation: each layer hands its rotated qkv to kv_hook(i, qkv)."""
-        if torch.is_grad_enabled():
-            raise RuntimeError("the prompt pass of generation runs under torch.no_grad()")
-        n = len(self.layers)
+    def each_layer(self, x, rows, step):
+        """The layer loop of every path (training, prompt pass, decode_step, extend) and the one statement of the top-rows rule:
+        x, left = step(i, layer, x, top) per layer, then the final norm.  `top` is `rows` for the top layer and None for every other;
+        a step whose layer ran on those rows alone returns left = None, one whose layer ran on every row hands `top` back.  Rows no
+        layer took (handed back, or HALVA_TOP_ROWS=0) are gathered behind the final norm."""
+        last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
-            top = rows if (rows is not None and TOP_ROWS and i == n - 1) else None
-            x = layer(x, info, use_lora, i > 0, top, lambda qkv, i=i: kv_hook(i, qkv))
-            if top is not None:
-                rows = None
+            if TOP_ROWS and i == last:
+                x, rows = step(i, layer, x, rows)
+            else:
+                x, _ = step(i, layer, x, None)
         x = self.norm(x)
         return x if rows is None else x.view(-1, x.shape[-1]).index_select(0, rows)
 

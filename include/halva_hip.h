@@ -323,7 +323,7 @@ int halva_decode_attn_chunked(const void* q, int64_t ldq, const void* kcache, co
  * so no workgroup reads a lens value written by its own launch.
  *
  * RoPE + append.  qkv: bf16 [B, n, 3, H, D], row i of sequence b at qkv[b * ldseq + i * ldrow].  For i < n_new[b], p = lens[b] + i: q and k of
- * the row rotated with row p of cos / sin (halva_decode_rope_append's arithmetic, bitwise), q in place, the rotated k and the plain v written
+ * the row rotated with row p of cos / sin (halva_decode_rope_append's arithmetic by construction: both kernels call one routine), q in place, the rotated k and the plain v written
  * to slot p.  Rows i >= n_new[b] are neither read nor written; a row with p >= min(Lcap, max_pos) is skipped (the caller refuses such calls;
  * nothing is written out of bounds).  One workgroup per (row, sequence). */
 int halva_extend_rope_append(void* qkv, int64_t ldrow, int64_t ldseq, const void* cos, const void* sin, int max_pos, void* kcache, void* vcache,
