@@ -11,7 +11,7 @@
 
 namespace {
 
-#include "sdpa_common.h"      // tile_off / mfma32 / frag_rows / frag_cols / Stage / store_rows_T: the attention kernels' tile pieces
+#include "sdpa_common.h"      // tile_off / mfma32 / frag_rows / frag_cols / Stage / store_rows_T, mask_half / half_max / xhalf_*: the attention kernels' tile pieces
 
 constexpr int kExtD = 128;                // head_dim of the decoder
 static_assert(kExtD == 8 * kRopeChunks, "rope_append_row serves this head_dim");
@@ -19,7 +19,6 @@ constexpr int kExtBM = 128;               // query rows per workgroup: 4 waves x
 constexpr int kExtBN = 64;                // keys per LDS tile
 constexpr int kExtWaves = kExtBM / 32;
 constexpr int kExtTileBytes = kExtBN * kExtD * 2;
-constexpr float kExtRescaleAt = 64.f;     // log2 units (sdpa_fwd.h: P stays below 2^64)
 
 // how many of the n rows of sequence b are new: n_new[b] cut to [0, n] and to the free slots of the cache
 __device__ __forceinline__ int ext_rows(int past, int nn, int n, int Lcap) { return max(min(min(nn, n), Lcap - past), 0); }
@@ -57,24 +56,8 @@ __global__ void extend_advance_kernel(int32_t* __restrict__ lens, const int32_t*
 // other rows of the wave, on B or on another sequence's n_new.  Key rows outside [0, past + n_new) are replaced by the nearest valid row
 // when the tile is staged (Stage::load_clamped) and masked to -inf; key past + j is visible to row i iff j <= i.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ext_xhalf_max(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float ext_xhalf_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float ext_half_max(const f32x16& st) {
-    float a = fmaxf(st[0], st[1]), b = fmaxf(st[2], st[3]);
-#pragma unroll
-    for (int r = 4; r < 16; r += 4) {
-        a = fmaxf(fmaxf(a, st[r]), st[r + 1]);
-        b = fmaxf(fmaxf(b, st[r + 2]), st[r + 3]);
-    }
-    return fmaxf(a, b);
-}
-// P = exp2(S sc - m) of one 32-key half: the bf16 B-operand fragments of the two 16-key slices, and the fp32 sum of the unrounded P
+// P = exp2(S sc - m) of one 32-key half: the bf16 B-operand fragments of the two 16-key slices, and the fp32 sum of the unrounded P.
+// Not sdpa_fwd.h's half_exp: scalar multiply and subtract, one running sum - the order tests/extend_ref_util.py models.
 __device__ __forceinline__ float ext_half_exp(const f32x16& st, float sc, float m, s16x8& p_lo, s16x8& p_hi) {
     float sum = 0.f;
 #pragma unroll
@@ -93,16 +76,6 @@ __device__ __forceinline__ float ext_half_exp(const f32x16& st, float sc, float 
     return sum;
 }
 template <bool MASK>
-__device__ __forceinline__ void ext_mask_half(f32x16& st, int kbase, int h, int len, int qpos) {
-    if (!MASK) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int kl = kbase + acc_row(r, h);
-        if (kl >= len || kl > qpos) st[r] = -INFINITY;
-    }
-}
-
-template <bool MASK>
 __device__ __forceinline__ void ext_tile(const char* kt, const char* vt, const s16x8 (&qf)[kExtD / 16], f32x16 (&oacc)[kExtD / 32], float& m_ref,
                                          float& l_run, float sc, int kv0, int len, int qpos, int lane) {
     constexpr int KS = kExtD / 16, DT = kExtD / 32;
@@ -114,10 +87,10 @@ __device__ __forceinline__ void ext_tile(const char* kt, const char* vt, const s
     for (int ks = 0; ks < KS; ++ks) s0 = mfma32(frag_rows<kExtD>(kt, 0, ks, lane), qf[ks], s0);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) s1 = mfma32(frag_rows<kExtD>(kt, 32, ks, lane), qf[ks], s1);
-    ext_mask_half<MASK>(s0, kv0, h, len, qpos);
-    ext_mask_half<MASK>(s1, kv0 + 32, h, len, qpos);
-    const float tmax = ext_xhalf_max(fmaxf(ext_half_max(s0), ext_half_max(s1))) * sc;      // (sc > 0; -inf when the row sees no key of the tile)
-    const bool move = tmax > m_ref + kExtRescaleAt;      // per row; the first tile (m_ref = -inf, key 0 visible) always moves
+    mask_half<MASK, true>(s0, kv0, h, len, qpos);
+    mask_half<MASK, true>(s1, kv0 + 32, h, len, qpos);
+    const float tmax = xhalf_max(fmaxf(half_max(s0), half_max(s1))) * sc;      // (sc > 0; -inf when the row sees no key of the tile)
+    const bool move = tmax > m_ref + kRescaleAt;      // per row; the first tile (m_ref = -inf, key 0 visible) always moves
     if (__any(move)) {
         const float m_next = move ? tmax : m_ref;
         const float alpha = move ? __builtin_amdgcn_exp2f(m_ref - m_next) : 1.f;      // exp2(-inf) = 0 on the first tile, where O = l = 0
@@ -213,7 +186,7 @@ __global__ __launch_bounds__(64 * kExtWaves, 2) void extend_attn_kernel(const bf
         __syncthreads();
     }
     if (!wave_live) return;
-    const float l_tot = ext_xhalf_sum(l_run);
+    const float l_tot = xhalf_sum(l_run);
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     bf16_t* orow = out + (int64_t)b * ld_out_seq + (int64_t)i * ld_out_row + hd * kExtD;
     store_rows_T<kExtD>(orow, oacc, inv, valid, lane);

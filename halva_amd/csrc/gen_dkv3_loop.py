@@ -222,7 +222,7 @@ def dma_groups():
             groups.append((pre if k == 0 else []) + g)
             k += 1
     stat = ["s_mov_b32 m0, %s" % S_DSTS, "s_nop 0", "buffer_load_dwordx4 %%[stat_voff], %s, %s offen lds" % (sq(SDESC), S_SOFFS), "s_add_u32 %s, %s, 512" % (S_SOFFS, S_SOFFS)]
-    groups.append([] if "nostat" in os.environ.get("DKV3_DIAG", "") else stat)      # (timing experiment: the statistics request and its scalar code gone)
+    groups.append(stat)
     ool += [".Ldkv3_sw%s_%%=:" % PHASE, "s_bitcmp1_b32 %s, 16" % S_DMALEFT, "s_cbranch_scc1 .Ldkv3_swb%s_%%=" % PHASE,      # already switched: nothing left
             "s_lshr_b32 %s, %s, 8" % (S_DMALEFT, S_DMALEFT), "s_or_b32 %s, %s, 0x10000" % (S_DMALEFT, S_DMALEFT),
             "s_and_b32 s97, %s, 0xff" % S_DMALEFT, "s_cmp_eq_u32 s97, 0", "s_cbranch_scc1 .Ldkv3_swb%s_%%=" % PHASE]            # no next item to serve
@@ -481,13 +481,6 @@ def main():
         else:
             expanded.append(l)
     lines = expanded
-    diag = os.environ.get("DKV3_DIAG", "")      # timing experiments only (results are wrong): nodma / nobar / nostore, comma separated
-    if "nodma" in diag:
-        lines = [l for l in lines if not l.startswith("global_load_lds") and not (l.startswith("buffer_load") and l.endswith(" lds"))]
-    if "nobar" in diag:
-        lines = [l for l in lines if l != "s_barrier" and not l.startswith("s_waitcnt vmcnt")]
-    if "nostore" in diag:
-        lines = [l for l in lines if not l.startswith("global_store")]
     with open(out, "w") as f:
         f.write("// generated by gen_dkv3_loop.py - do not edit (python3 gen_dkv3_loop.py)\n")
         for l in lines:

@@ -15,17 +15,9 @@ constexpr float kLn2 = 0.6931471805599453f;
 constexpr int kNW = 4;   // waves per workgroup
 
 // Round 6: the logits rows are streamed - a 0.5 GB chunk is read once per pass and overwritten in place by the gradient - so
-// the row kernels' policy applies: nontemporal loads and stores (-DHALVA_LOSS_NT=0: the plain accesses of rounds 1-5, A/B builds).
-#ifndef HALVA_LOSS_NT
-#define HALVA_LOSS_NT 1
-#endif
-#if HALVA_LOSS_NT
+// the row kernels' policy applies: nontemporal loads and stores (rounds 1-5 used plain accesses).
 #define LOSS_LOAD(p) __builtin_nontemporal_load(p)
 #define LOSS_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define LOSS_LOAD(p) (*(p))
-#define LOSS_STORE(p, v) (*(p) = (v))
-#endif
 
 template <typename T>
 struct RowIO;

@@ -21,8 +21,11 @@
 //   sdpa_bwd_dq2_kernel (*)    sdpa_bwd_dq2.h    pass 3: dQ = dS K (HALVA_DQ2_FAST_TILE=0: every tile through the general per-strip loop)
 //   sdpa_bwd_dq_kernel         sdpa_bwd_dq.h     the 3-product dQ (forms delta itself): head_dim 64 and calls without a workspace, in front of sdpa_bwd_dkv2
 // sdpa_common.h holds what they share: SdpaParams, the branch mask, LDS tiles (one XOR swizzle, conflict-free for ds_read_b128 row reads
-// and transposed reads) and their LDS-DMA, the store epilogues (with the inverse RoPE), the block maps.
+// and transposed reads) and their LDS-DMA, the softmax pieces of a score tile (mask_half, half_max, xhalf_max / xhalf_sum, kRescaleAt: also
+// what extend.hip's attention uses), the store epilogues (with the inverse RoPE), the block maps.
 // No atomics on results: dQ has its own kernels, so results are bitwise reproducible.
+// Each kernel is compiled ONE way: the only -D switches are HALVA_STAMP / HALVA_STAMP_STRIDE (the in-kernel clock); the variants that were
+// measured and retired are described in DESIGN.md 5.3.
 #include "common.h"
 
 #include <algorithm>
@@ -59,7 +62,6 @@ struct SdpaSwitches {
     int dkv3_order = kOrderUnset;      // HALVA_DKV3_ORDER: order of the items inside a work queue (sdpa_dkv3.h)
     bool rope_fused_bwd = false; // HALVA_ROPE_FUSED_BWD=0: dq / dk leave the backward un-rotated, the rotation follows as its own launch
     bool dq2_fast_tile = true;   // HALVA_DQ2_FAST_TILE=0: every tile of sdpa_bwd_dq2 through the general per-strip path
-    long long ds_evict_mb = -1;  // HALVA_DS_EVICT_MB (experiments/ds_residency: read and acted on in -DHALVA_DS_EVICT_EXP builds only)
 };
 // fwd3_call: a causal head_dim-128 forward; ds_call: a head_dim-128 backward with a workspace - the calls the respective switches can bear on
 SdpaSwitches read_switches(bool fwd3_call, bool ds_call) {
@@ -79,9 +81,6 @@ SdpaSwitches read_switches(bool fwd3_call, bool ds_call) {
             if ((sw.dkv3_asm = on("HALVA_DKV3_ASM"))) sw.rope_fused_bwd = on("HALVA_ROPE_FUSED_BWD");
         }
         sw.dq2_fast_tile = on("HALVA_DQ2_FAST_TILE");
-#ifdef HALVA_DS_EVICT_EXP
-        if (const char* e = getenv("HALVA_DS_EVICT_MB")) sw.ds_evict_mb = atoll(e);
-#endif
     }
     return sw;
 }
@@ -114,11 +113,10 @@ struct BwdPlan {
     bool slow_tr;           // (dkv2, dq, dq2_fast)
     bool rope_fused;        // the store epilogues rotate dq / dk; false: they leave un-rotated (halva_sdpa_branch_bwd_rope follows up)
     int sched_order;        // sdpa_bwd_dkv3 only
-    long long ds_evict_mb;  // (-DHALVA_DS_EVICT_EXP builds only) MiB to memset between the dK/dV and the dQ kernel, < 0: none
 };
 template <int D, bool CAUSAL>
 BwdPlan choose_bwd(int S, int T, int H, int64_t ld_qkv, int64_t ld_do, bool have_ws, bool have_lse2, bool have_rope, const SdpaSwitches& sw) {
-    BwdPlan plan{false, DkvKernel::dkv2, DqKernel::dq, sw.slow_tr, false, 0, sw.ds_evict_mb};
+    BwdPlan plan{false, DkvKernel::dkv2, DqKernel::dq, sw.slow_tr, false, 0};
     if (!(have_ws && D == 128)) return plan;      // head_dim 64, calls without a workspace: the 3-product dQ and the two-role dK/dV, no rotation
     plan.ds_path = true;
     const int64_t rows = (int64_t)S * T;
@@ -132,9 +130,8 @@ BwdPlan choose_bwd(int S, int T, int H, int64_t ld_qkv, int64_t ld_do, bool have
         plan.sched_order = sw.dkv3_order != kOrderUnset ? sw.dkv3_order : (CAUSAL ? 2 : 0);
     }
     // the inverse RoPE of dq / dk rides in the store epilogues of sdpa_bwd_dq2 and of sdpa_bwd_dkv3's generated build; any other kernel
-    // combination leaves them un-rotated.  (DKV3_ROWS_VIA_LDS: the dK rows are rotated by dkv3_store_rows_lds only - a -DDKV3_ROWS_VIA_LDS=0
-    // build stores them un-rotated, so it must not report the rotation as done)
-    plan.rope_fused = have_rope && plan.dkv == DkvKernel::dkv3_asm && DKV3_ROWS_VIA_LDS && sw.rope_fused_bwd;
+    // combination leaves them un-rotated
+    plan.rope_fused = have_rope && plan.dkv == DkvKernel::dkv3_asm && sw.rope_fused_bwd;
     plan.dq = sw.slow_tr || sw.dq2_fast_tile ? DqKernel::dq2_fast : DqKernel::dq2_general;      // (the SLOW_TR build has the fast tile only)
     return plan;
 }
@@ -223,19 +220,6 @@ int launch_bwd(SdpaParams p, int S, hipStream_t st, const BwdPlan& plan) {
         return launch<sdpa_bwd_dkv3_kernel<128, CAUSAL, decltype(use_asm)::value>>("sdpa_bwd_dkv3", n_wg(p, false), kPerCu, 256, DKV3_LDS, st, p);
     });
     if (rc != HALVA_OK) return rc;
-#ifdef HALVA_DS_EVICT_EXP      // experiments/ds_residency only: push the dS just written out of the Infinity Cache before the dQ kernel reads it
-    if (plan.ds_evict_mb >= 0) {
-        static char* scratch = nullptr;
-        static size_t scratch_bytes = 0;
-        const size_t want = (size_t)plan.ds_evict_mb << 20;
-        if (want > scratch_bytes) {
-            if (scratch) (void)hipFree(scratch);
-            (void)hipMalloc(&scratch, want);
-            scratch_bytes = want;
-        }
-        if (want) (void)hipMemsetAsync(scratch, 0, want, st);
-    }
-#endif
     const size_t lds_dq2 = 3 * 64 * D * 2 + 8 * 3 * DS_LDS_SLOT;
     if (plan.dq == DqKernel::dq2_general)
         return launch<sdpa_bwd_dq2_kernel<D, false, false>>("sdpa_bwd_dq2 (general tile)", n_wg(p256, true), 0, 512, lds_dq2, st, p256);

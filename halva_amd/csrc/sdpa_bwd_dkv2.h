@@ -44,14 +44,11 @@ __device__ __forceinline__ DkvGeom dkv_geom(const SdpaParams& p, int kb, int str
 // of in the next block's prologue (measured per block, s_memtime: 10 000-12 000 cycles from entry to the first step, of which three
 // memory round trips one behind the other; a step is ~3 850).
 //   kb_next: the key block this workgroup runs next (-1: none)      prefetched: this block's operands were requested by its predecessor
-#ifndef HALVA_DKV_CINIT
-#define HALVA_DKV_CINIT 1
-#endif
-// HALVA_DKV_CINIT (default): a row constant as the initial accumulator (cdna_hip_programming.md, attention backward), on the K side: the
+// A row constant as the initial accumulator (cdna_hip_programming.md, attention backward), on the K side: the
 // dP = dO V^T chain starts from -delta (exact: the same fp32 additions in another order), so dZ = P * dP' needs no subtraction - 32
 // vector instructions fewer per K-side wave and step, and the 32 registers that held delta during the vector work are free after each
 // chain's first MFMA.  The V side's analogue (S chain from -lse, K pre-multiplied by scale * log2 e so that P = exp2(S')) is NOT
-// taken: like HALVA_FWD_CINIT it needs a second bf16 rounding of an operand, which moves P by up to ~1 % (see fwd_tile).
+// taken: it needs a second bf16 rounding of an operand, which moves P by up to ~1 % (the forward tried it: see fwd_tile).
 template <int D, bool CAUSAL, bool SLOW_TR, int ROLE>
 __device__ __forceinline__ void sdpa_bwd_dkv2_block(const SdpaParams& p, char* smem, int s, int hd, int kb, int kb_next, bool prefetched,
                                                     int strip, int start, int len, const Branch br, s16x8 (&sf)[D / 16], float (&st)[2]) {
@@ -97,11 +94,7 @@ __device__ __forceinline__ void sdpa_bwd_dkv2_block(const SdpaParams& p, char* s
     auto store_stats = [&](int buf) {
         if (stats_wave) {
             lse_lds[buf * BQ + lane] = st_lse * kLog2e;
-#if HALVA_DKV_CINIT      // stored NEGATED: the values are the initial accumulator of the K side's dP chain (see below)
-            dlt_lds[buf * BQ + lane] = -st_dlt;
-#else
-            dlt_lds[buf * BQ + lane] = st_dlt;
-#endif
+            dlt_lds[buf * BQ + lane] = -st_dlt;      // stored NEGATED: the values are the initial accumulator of the K side's dP chain (see below)
         }
     };
     // The four V-side waves fetch the tiles: they finish a step's arithmetic ahead of their K-side partners (measured against
@@ -219,7 +212,7 @@ __device__ __forceinline__ void sdpa_bwd_dkv2_block(const SdpaParams& p, char* s
                 // Every LDS read is placed by hand one block ahead of its use and nothing may cross a slot boundary: left to itself the
                 // scheduler hoists all reads to the top of the step and the register allocator spills.
 #define SLOT() __builtin_amdgcn_sched_barrier(0)
-                constexpr bool CINIT = HALVA_DKV_CINIT && ROLE == 1;          // K side: the dP chain starts from -delta
+                constexpr bool CINIT = ROLE == 1;         // K side: the dP chain starts from -delta
                 constexpr int PPS = 8 / KS, PPD = 8 / (2 * DT), NS = KS;      // NS slots per block (KS == 2 * DT)
                 static_assert(KS == 2 * DT, "slot count");
                 const float* stat_t = ROLE ? dlt_t : lse_t;
@@ -228,8 +221,7 @@ __device__ __forceinline__ void sdpa_bwd_dkv2_block(const SdpaParams& p, char* s
                     (void)t0, (void)t1;
                     if (ROLE == 0)
                         return pack_bf16x2(__builtin_amdgcn_exp2f(__builtin_fmaf(x[r], sc, -t0)), __builtin_amdgcn_exp2f(__builtin_fmaf(x[r + 1], sc, -t1)));
-                    if (CINIT) return pack_bf16x2(bf16_lo(pw) * x[r], bf16_hi(pw) * x[r + 1]);      // x = dP - delta already
-                    return pack_bf16x2(bf16_lo(pw) * (x[r] - t0), bf16_hi(pw) * (x[r + 1] - t1));
+                    return pack_bf16x2(bf16_lo(pw) * x[r], bf16_hi(pw) * x[r + 1]);      // K side: x = dP - delta already
                 };
                 auto mask_scores = [&](f32x16& x, int q0) {
                     const bool lane_off = !k_valid || (q_in_b && key_hidden);

@@ -73,12 +73,6 @@ __device__ __forceinline__ int ds_piece_off(int key, int qgroup) {      // byte 
 // factor of two by an XOR of the chunk position, applied by the LDS-DMA lanes (lane l fetches chunk l ^ swizzle; LDS-DMA writes lane l to
 // byte 16 l) - zero conflicts, but the requests no longer ask for their 1 KiB in lane order and the kernel, which is HBM-bound, ran 1.6 % SLOWER
 // (950-959 -> 971-973 us at the step's shapes, same box).
-#ifndef DQ2_FAST_TILE
-#define DQ2_FAST_TILE 1      // (0: every tile through the general per-strip path, as before round 5)
-#endif
-#ifndef HALVA_DQ2_DS_POLICY
-#define HALVA_DQ2_DS_POLICY " nt"      // (experiments/ds_residency builds it with "" as well)
-#endif
 constexpr int DS_LDS_PIECE = 1024 + 128, DS_LDS_STRIP = 2 * DS_LDS_PIECE, DS_LDS_SLOT = 2 * DS_LDS_STRIP;
 __device__ __forceinline__ int ds_lds_off(int key, int qgroup) {      // (inside a strip)
     return DS_LDS_PIECE * (qgroup >> 2) + 16 * (key + 32 * (qgroup & 1)) + 8 * ((qgroup >> 1) & 1);
@@ -123,13 +117,9 @@ __device__ __forceinline__ void sdpa_bwd_dq2_block(const SdpaParams& p, char* sm
         return wave_in_b && k0 >= br.a && k0 + 31 < br.b;
     };
     // requests of one tile by this wave: its 2 chunks of the shared K tile, and - while the tile is live for it - its own 4 KiB of dS
-    // (-DHALVA_DQ2_DIAG=<bits>, timing experiments only - results are wrong: 1 no matrix work, 2 no dS requests, 4 no K requests, 8 no barriers)
-#ifndef HALVA_DQ2_DIAG
-#define HALVA_DQ2_DIAG 0
-#endif
     auto stage = [&](int kt, int slot) {
-        if (!(HALVA_DQ2_DIAG & 4)) stage_tile_dma<D, NW>(k_lds + slot * TILE_BYTES, kp, p.ld_qkv, krow0, kt * BN - start, len, wave, lane);
-        if (!(HALVA_DQ2_DIAG & 2) && tile_live(kt)) {
+        stage_tile_dma<D, NW>(k_lds + slot * TILE_BYTES, kp, p.ld_qkv, krow0, kt * BN - start, len, wave, lane);
+        if (tile_live(kt)) {
             const char* src = ds_pair + ((int64_t)(kt >> 1) * p.ds_nt + step) * 16384 + 2 * (kt & 1) * 4096 + sub * 2048;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {                 // strip c >> 1, register half c & 1
@@ -138,7 +128,7 @@ __device__ __forceinline__ void sdpa_bwd_dq2_block(const SdpaParams& p, char* sm
                 const char* rows = src + (c >> 1) * 4096 + (c & 1) * 1024;
                 unsigned keep;
                 // nt: these bytes are read once, by this CU only - they must not evict the K tiles the XCD's workgroups share in L2
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3" HALVA_DQ2_DS_POLICY "\n\ts_mov_b32 m0, %0"
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 nt\n\ts_mov_b32 m0, %0"
                              : "=&s"(keep) : "v"(voff), "s"(dst), "s"(rows) : "memory");
             }
         }
@@ -157,12 +147,7 @@ __device__ __forceinline__ void sdpa_bwd_dq2_block(const SdpaParams& p, char* sm
     // is 21 of the 33..54 tiles of each of the six B blocks - 30 % of this kernel's tile steps, each a 16-KiB K tile and up to 32 KiB
     // of dS fetched for nothing.  (Branch points come with start == 0: halva_amd/splice.py packs right-padded rows only.)
     int skip_lo = ntile_end, skip_hi = ntile_end;
-#ifndef HALVA_DQ2_NO_SKIP      // (A/B switch: -DHALVA_DQ2_NO_SKIP walks every tile as round 2 did)
-    if (start == 0 && lq0 >= br.b)
-#else
-    if (false)
-#endif
-    {
+    if (start == 0 && lq0 >= br.b) {
         skip_lo = min(ntile_end, max(first_tile, (br.a + BN - 1) / BN));
         skip_hi = max(skip_lo, min(ntile_end, br.b / BN));
     }
@@ -178,25 +163,17 @@ __device__ __forceinline__ void sdpa_bwd_dq2_block(const SdpaParams& p, char* sm
         const int slot = i % RING;
         // tile i has landed: everything but the requests of tile i + 1 (2 pieces, 6 while that tile is live for this wave)
         if (i + 1 < n_walk) {
-            if (HALVA_DQ2_DIAG & 6) {      // (diagnostic builds: fewer requests per tile)
-                const bool live = tile_live(tile_at(i + 1));
-                if ((HALVA_DQ2_DIAG & 6) == 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (HALVA_DQ2_DIAG & 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else if (live) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else if (tile_live(tile_at(i + 1))) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if (tile_live(tile_at(i + 1))) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (HALVA_DQ2_DIAG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        else
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // ... for every wave; and tile i - 1 has been read by all
         if (i + 2 < n_walk) stage(tile_at(i + 2), (slot + 2) % RING);         // into the slot of tile i - 1
-        if (!(HALVA_DQ2_DIAG & 1) && tile_live(kt)) {
+        if (tile_live(kt)) {
             const char* ktile = k_lds + slot * TILE_BYTES;
             const char* dst_t = ds_lds + slot * DS_LDS_SLOT;
-            if (DQ2_FAST_TILE && FAST && !SLOW_TR) {
+            if (FAST && !SLOW_TR) {
                 // All 40 operand reads of the tile from three per-lane bases + immediates, asked for ahead of the 16 products (the same products in the
                 // same order as the general path below: identical sums).  Compiled from the loop below, every product waited for operand reads issued just
                 // in front of it (s_waitcnt lgkmcnt(0) x 16 per tile) and each read cost two vector instructions of address arithmetic: without any dS

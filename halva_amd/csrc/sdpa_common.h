@@ -1,5 +1,5 @@
 // A fragment of the sdpa.hip translation unit, not compiled alone: included there inside its anonymous namespace, behind common.h and
-// the sdpa_*.h listed before it.  Holds what the attention kernels share (vector types, STAMP, SdpaParams, Branch, tiles and their LDS-DMA, store epilogues, block maps).
+// the sdpa_*.h listed before it.  Holds what the attention kernels share (vector types, STAMP, SdpaParams, Branch, tiles and their LDS-DMA, the softmax tile pieces, store epilogues, block maps).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
@@ -170,6 +170,41 @@ __device__ __forceinline__ s16x8 acc_to_frag(const f32x16& x, int s) {
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // ---------------------------------------------------------------------------------------------------
+// softmax pieces of a [32 keys x 32 queries] score accumulator (the query on the lane, its other 16 keys on the lane 32 away)
+// ---------------------------------------------------------------------------------------------------
+// a row's exponent reference moves only when its maximum exceeds it by more than this (log2 units: P stays below 2^64, far inside fp32 /
+// bf16 range)
+constexpr float kRescaleAt = 64.f;
+
+__device__ __forceinline__ float xhalf_max(float v) {   // max with the lane 32 away (v_permlane32_swap: no LDS round trip)
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float xhalf_sum(float v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// keys at or beyond len, and under CAUSAL keys behind the lane's query ql, to -inf
+template <bool MASK, bool CAUSAL>
+__device__ __forceinline__ void mask_half(f32x16& st, int kbase, int h, int len, int ql) {
+    if (!MASK) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int kl = kbase + acc_row(r, h);
+        if (kl >= len || (CAUSAL && kl > ql)) st[r] = -INFINITY;
+    }
+}
+__device__ __forceinline__ float half_max(const f32x16& st) {
+    float a = fmaxf(st[0], st[1]), b = fmaxf(st[2], st[3]);
+#pragma unroll
+    for (int r = 4; r < 16; r += 4) {
+        a = fmaxf(fmaxf(a, st[r]), st[r + 1]);
+        b = fmaxf(fmaxf(b, st[r + 2]), st[r + 3]);
+    }
+    return fmaxf(a, b);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // cooperative tile staging: ROWS x D bf16, 256 threads, register staged
 // ---------------------------------------------------------------------------------------------------
 template <int D, int ROWS, int NT = 256>
@@ -264,16 +299,8 @@ __device__ __forceinline__ void stage_tile_dma_wait() { __builtin_amdgcn_s_waitc
 // and the store tail of a row block is bound by the NUMBER of store instructions (measured: ~5 600 cycles for a V-side wave of the
 // dK/dV kernel, ~10 000 for the K-side wave that finishes last).  v_permlane32_swap trades the pieces of two neighbouring groups
 // between the two lanes of a row, after which each holds 16 contiguous bytes: 8 stores per lane, same bytes, same addresses.
-// the dq / dk / dv rows leave through this.  -DHALVA_ROWS_NT=1 (with FWD3_O_NT=1 for the forward's generator) writes them nontemporally: measured
-// round 5 and NOT kept - sdpa_bwd_dq2 +4 %, sdpa_bwd_dkv3 +0.5 %, sdpa_fwd3 +0.6 % at the step's shapes (alternating runs, rocprofv3)
-#ifndef HALVA_ROWS_NT
-#define HALVA_ROWS_NT 0
-#endif
-#if HALVA_ROWS_NT
-#define HALVA_ROW_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define HALVA_ROW_STORE(ptr, val) (*(ptr) = (val))
-#endif
+// the o / dq / dk / dv rows leave through this with plain stores: nontemporal ones measured sdpa_bwd_dq2 +4 %, sdpa_bwd_dkv3 +0.5 %,
+// sdpa_fwd3 +0.6 % at the step's shapes (alternating runs, rocprofv3; DESIGN.md, "Retired kernel variants")
 // one [32 x 32] tile of a transposed accumulator (columns 32 dt .. 32 dt + 31 of the lanes' rows): two 16-byte stores per lane
 __device__ __forceinline__ void store_tile_T(bf16_t* row_ptr_dt, const f32x16& t, float mul, int h) {
 #pragma unroll
@@ -288,7 +315,7 @@ __device__ __forceinline__ void store_tile_T(bf16_t* row_ptr_dt, const f32x16& t
         // upper lanes' group-2gp words <-> lower lanes' group-(2gp+1) words
         const auto x = __builtin_amdgcn_permlane32_swap(w[0][0], w[1][0], false, false);
         const auto y = __builtin_amdgcn_permlane32_swap(w[0][1], w[1][1], false, false);
-        HALVA_ROW_STORE(reinterpret_cast<u32x4*>(row_ptr_dt + 16 * gp + 8 * h), (u32x4{x[0], y[0], x[1], y[1]}));
+        *reinterpret_cast<u32x4*>(row_ptr_dt + 16 * gp + 8 * h) = u32x4{x[0], y[0], x[1], y[1]};
     }
 }
 template <int D>

@@ -28,9 +28,6 @@ constexpr int DKV3_ND = DKV3_LSE + 4 * 64 * 4;              // (the plain-HIP tw
 constexpr int DKV3_SCHED = DKV3_LSE + 4096;                  // [2][64] ints: the persistent workgroup's item mail box (two item records, sdpa_dkv3_items.h; gen_dkv3_loop.py:MAIL_LDS)
 constexpr int DKV3_STAGE = DKV3_SCHED + 512;                 // [4 waves][4 KiB]: a wave's staging area for its dK / dV rows (dkv3_store_rows_lds)
 constexpr int DKV3_LDS = DKV3_STAGE + 4 * 4096;
-#ifndef DKV3_ROWS_VIA_LDS
-#define DKV3_ROWS_VIA_LDS 1      // 0: the dK / dV rows stored straight from the accumulator layout (store_rows_T), rounds 2-3
-#endif
 
 __device__ __forceinline__ unsigned dkv3_uni(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ unsigned long long dkv3_uni64(const void* ptr) {
@@ -165,7 +162,7 @@ __device__ __forceinline__ void dkv3_store_rows_lds(char* smem, int wave, bf16_t
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const u32x4 v = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(rd[j & 1] + 1024 * j);
-            if (8 * j + rr < rows_ok) HALVA_ROW_STORE(reinterpret_cast<u32x4*>(row0 + (int64_t)(8 * j + rr) * ld + 64 * pass + 8 * rc), v);
+            if (8 * j + rr < rows_ok) *reinterpret_cast<u32x4*>(row0 + (int64_t)(8 * j + rr) * ld + 64 * pass + 8 * rc) = v;
         }
     }
 }
@@ -403,9 +400,6 @@ __device__ __forceinline__ void sdpa_bwd_dkv3_items(const SdpaParams& p, char* s
             // Round 6 tried to get rid of both (experiments/dkv3_item_boundary: the loads in front of / between / behind the PREVIOUS item's store
             // conversions; a second register set a192-a255 filled by the previous block's first call): the issue time cannot be hidden by a wave
             // that is alone on its SIMD, and none of the five variants beat this one.
-#ifdef DKV3_DIAG_NO_KV      // (timing experiment, results wrong: what would FREE K / V fragments buy? - the ceiling of any other way to deliver them)
-            if (round == 0)
-#endif
             {
                 const unsigned long long k0 = ((unsigned long long)(unsigned)DKV3_F(rec, K_HI) << 32) | (unsigned)DKV3_F(rec, K_LO);
                 const char* k_ptr = (const char*)(size_t)k0 + (unsigned long long)(unsigned)min(max(kl, 0), len - 1) * ld2 + 16 * h;
@@ -467,7 +461,7 @@ __device__ __forceinline__ void sdpa_bwd_dkv3_items(const SdpaParams& p, char* s
 #undef DKV3_FIRST
             }
             // (straight behind the loop, in the same block: carried to a common tail the accumulators travelled through vector registers)
-            if (DKV3_ROWS_VIA_LDS) {      // (rows of the wave in the tensor: uniform)
+            {      // the dK / dV rows leave transposed through LDS (rows of the wave in the tensor: uniform)
                 const int rows_ok = wave_u == 0 ? DKV3_F(rec, ROWS_OK0) : wave_u == 1 ? DKV3_F(rec, ROWS_OK1) : wave_u == 2 ? DKV3_F(rec, ROWS_OK2) : DKV3_F(rec, ROWS_OK3);
                 const unsigned long long dk0 = ((unsigned long long)(unsigned)DKV3_F(rec, DK_HI) << 32) | (unsigned)DKV3_F(rec, DK_LO);
                 // (through a GLOBAL-typed pointer: an address built from integers is a generic one to the compiler, and generic stores are FLAT
@@ -491,13 +485,6 @@ __device__ __forceinline__ void sdpa_bwd_dkv3_items(const SdpaParams& p, char* s
                     dkv3_store_rows_lds<true, true>(smem, wave, w0, p.ld_qkv, accK, p.scale, rows_ok, lane, rope_c, rope_s);
                 } else {
                     dkv3_store_rows_lds<false, true>(smem, wave, w0, p.ld_qkv, accK, p.scale, rows_ok, lane, nullptr, nullptr);
-                }
-            } else {
-                const int gk = DKV3_F(rec, KB) * 128 + 32 * wave + (lane & 31);
-                bf16_t* dk_row = p.dk + ((int64_t)DKV3_F(rec, S) * p.T + gk) * p.ld_qkv + DKV3_F(rec, HD) * D;
-                if (gk < p.T) {
-                    store_rows_T<D>((bf16_t*)((char*)dk_row + dv_minus_dk), accV, k_valid ? 1.f : 0.f, true, lane);
-                    store_rows_T<D>(dk_row, accK, k_valid ? p.scale : 0.f, true, lane);
                 }
             }
             ring_base = (ring_base + ntiles) & 3;      // (the next item's prefetched tiles continue the slot rotation)

@@ -54,20 +54,15 @@ __device__ __forceinline__ Dkv3Call dkv3_call_params(int t, int q_begin, int kbl
     const bool q_in_b = qt0 >= br.b;                     // br.b and qt0 are multiples of 64: uniform over the step
     Dkv3Call c;
     c.t_side = q_in_b ? ntiles : min(ntiles, (int)(((int64_t)br.b - q_begin + BQ - 1) / BQ));      // first step at or behind br.b
-#ifdef HALVA_DKV3_ALL_MASKED      // diagnostic: every step through the masked phase (same results: an interior step's masks pass everything)
-    c.n0 = c.t_side - t, c.n1 = 0, c.n2 = 0;
-#else
-    {      // interior(t') on this side of br.b = side_ok && t_diag <= t' < t_full: three runs, no scan
-        const bool all_valid = kblk_min >= 0 && kblk_min + 128 <= len;      // workgroup-uniform: no padded key in the block
-        const bool side_ok = all_valid && !(q_in_b && kblk_min < br.b && kblk_min + 127 >= br.a);
-        const int t_diag = CAUSAL ? max(0, (kblk_min + 127 - q_begin + BQ - 1) / BQ) : 0;      // first t' with qt0 >= kblk_min + 127
-        const int t_full = max(0, (len - q_begin) / BQ);                                          // first t' with qt0 + 64 > len
-        const int lo = min(c.t_side, max(t, t_diag)), hi = min(c.t_side, max(lo, t_full));
-        c.n0 = side_ok ? lo - t : c.t_side - t;
-        c.n1 = side_ok ? hi - lo : 0;
-        c.n2 = c.t_side - t - c.n0 - c.n1;
-    }
-#endif
+    // interior(t') on this side of br.b = side_ok && t_diag <= t' < t_full: three runs, no scan
+    const bool all_valid = kblk_min >= 0 && kblk_min + 128 <= len;      // workgroup-uniform: no padded key in the block
+    const bool side_ok = all_valid && !(q_in_b && kblk_min < br.b && kblk_min + 127 >= br.a);
+    const int t_diag = CAUSAL ? max(0, (kblk_min + 127 - q_begin + BQ - 1) / BQ) : 0;      // first t' with qt0 >= kblk_min + 127
+    const int t_full = max(0, (len - q_begin) / BQ);                                          // first t' with qt0 + 64 > len
+    const int lo = min(c.t_side, max(t, t_diag)), hi = min(c.t_side, max(lo, t_full));
+    c.n0 = side_ok ? lo - t : c.t_side - t;
+    c.n1 = side_ok ? hi - lo : 0;
+    c.n2 = c.t_side - t - c.n0 - c.n1;
     const int n = c.t_side - t;
     c.ndma = min(n, max(0, ntiles - 3 - t));
     c.part = last_partial && c.ndma > 0 && (t + c.ndma - 1 + 3 == ntiles - 1);

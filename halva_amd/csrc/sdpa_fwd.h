@@ -7,20 +7,11 @@
 // tile t+1 are issued before the MFMAs of tile t and written to LDS after them; one barrier per tile).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float xhalf_max(float v) {   // max with the lane 32 away (v_permlane32_swap: no LDS round trip)
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // The tile body is two straight-line blocks in which the wave's own vector work rides in the shadow of its own MFMAs
 // (the interleave is written out in the source and pinned with scheduling fences):
 //   A:  S0 = K[0:32] Q^T ; S1 = K[32:64] Q^T  ||  max(S0), P0 = exp2(S0*sc - m_ref), sum      then max(S1)
 //   B:  O^T += V^T[:, 0:32] P0^T              ||  P1 = exp2(S1*sc - m_ref), sum ;  O^T += V^T[:, 32:64] P1^T
-// The exponent reference m_ref is only moved when a row's maximum exceeds it by more than 2^RESCALE_AT (the first tile
+// The exponent reference m_ref is only moved when a row's maximum exceeds it by more than 2^kRescaleAt (the first tile
 // always does): that rare path sits between A and B, rescales O / l and recomputes P0 from the untouched S0; O is not
 // multiplied every tile.  Cross-half reductions use v_permlane32_swap (no LDS round trip), the exp2 argument / row sums use
 // packed fp32 ops, full tiles are fetched by pointer bumps (no per-tile 64-bit address arithmetic).
@@ -29,24 +20,6 @@ __device__ __forceinline__ float xhalf_sum(float v) {
 // per tile; the later-dispatched wave of each SIMD is starved whatever s_setprio says); the same with the two blocks in
 // rotated order and one barrier; 4-wave workgroups at two per CU.
 // ---------------------------------------------------------------------------------------------------
-template <bool MASK, bool CAUSAL>
-__device__ __forceinline__ void mask_half(f32x16& st, int kbase, int h, int len, int ql) {
-    if (!MASK) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int kl = kbase + acc_row(r, h);
-        if (kl >= len || (CAUSAL && kl > ql)) st[r] = -INFINITY;
-    }
-}
-__device__ __forceinline__ float half_max(const f32x16& st) {
-    float a = fmaxf(st[0], st[1]), b = fmaxf(st[2], st[3]);
-#pragma unroll
-    for (int r = 4; r < 16; r += 4) {
-        a = fmaxf(fmaxf(a, st[r]), st[r + 1]);
-        b = fmaxf(fmaxf(b, st[r + 2]), st[r + 3]);
-    }
-    return fmaxf(a, b);
-}
 // One 2-element slice of P = exp2(S * sc - m): elements r, r+1 of the accumulator -> bf16 pair in the B-operand fragment
 __device__ __forceinline__ void exp_pair(const f32x16& st, int r, f32x2 sc2, f32x2 ms2, f32x2& ps, s16x8& p_lo, s16x8& p_hi) {
     f32x2 x = {st[r], st[r + 1]};
@@ -70,35 +43,6 @@ __device__ __forceinline__ float half_exp(const f32x16& st, float sc, float m_su
     return ps[0] + ps[1];
 }
 
-// The same for scores that come out of the MFMA chain already scaled and shifted (the chain's initial accumulator holds -m_ref and
-// Q was multiplied by scale * log2(e) once per row block): P = exp2(S'), no per-element multiply-add at all.
-__device__ __forceinline__ void exp_pair0(const f32x16& st, int r, f32x2& ps, s16x8& p_lo, s16x8& p_hi) {
-    const f32x2 e = {__builtin_amdgcn_exp2f(st[r]), __builtin_amdgcn_exp2f(st[r + 1])};
-    ps = ps + e;
-    const unsigned w = pack_bf16x2(e[0], e[1]);
-    if (r < 8) {
-        p_lo[r] = (short)(w & 0xffffu);
-        p_lo[r + 1] = (short)(w >> 16);
-    } else {
-        p_hi[r - 8] = (short)(w & 0xffffu);
-        p_hi[r - 7] = (short)(w >> 16);
-    }
-}
-__device__ __forceinline__ float half_exp0(const f32x16& st, s16x8& p_lo, s16x8& p_hi) {
-    f32x2 ps = {0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) exp_pair0(st, r, ps, p_lo, p_hi);
-    return ps[0] + ps[1];
-}
-// bf16 fragment * c, rounded to bf16 again (once per row block, on the Q fragments)
-__device__ __forceinline__ s16x8 scale_frag(const s16x8& f, float c) {
-    const u32x4 w = __builtin_bit_cast(u32x4, f);
-    u32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(bf16_lo(w[i]) * c, bf16_hi(w[i]) * c);
-    return __builtin_bit_cast(s16x8, o);
-}
-
 // scheduling fence that only LDS reads and scalar ops may cross: pins the MFMA / VALU interleave written in the source
 #define FENCE() __builtin_amdgcn_sched_barrier(0x100 | 0x004)
 
@@ -109,43 +53,29 @@ __device__ __forceinline__ s16x8 scale_frag(const s16x8& f, float c) {
 #define STAMP_ARGS
 #define STAMP_PASS
 #endif
-#ifndef HALVA_FWD_CINIT
-#define HALVA_FWD_CINIT 0
-#endif
-// HALVA_FWD_CINIT=1 (measured in round 3, NOT the default): the row constant rides in the MFMA chain.  `qf` holds Q * (scale * log2 e) (bf16, rounded once per row
-// block) and both score chains start from the accumulator `minit` = -m_ref in every register (the query sits on the lane), so a score
-// leaves the matrix pipe as S' = log2(e) * scale * q.k - m_ref and P = exp2(S') costs ONE vector instruction per element instead of a
-// multiply-add plus the exponential (32 fewer vector instructions per wave and tile).  Measured on MI355X: forward 379 -> 372 us (-1.8 %),
-// and REJECTED for its numerics: the extra bf16 rounding of Q * c moves a score by ~2^-9 of its magnitude, i.e. P by up to ~1 % for
-// scores of a few tens - test_sdpa_exponent_reference_moves_when_later_keys_dominate (scores of 90..230 nat) leaves its 1e-2 bound
-// (2.1e-2) and the full-width grouping / prefix-sharing invariance tests see 3x their usual loss noise.  flash-attn keeps the scale
-// in fp32 after the product for the same reason; so does the default build.
+// The scale stays in fp32 and is applied after the product (a multiply-add in front of every exponential), as flash-attn does.  Folding it
+// and -m_ref into the MFMA chain (Q * scale * log2 e rounded to bf16 once per row block, the chains started from -m_ref) measured -1.8 % and
+// was rejected for its numerics: 2.1e-2 against the 1e-2 bound of test_sdpa_exponent_reference_moves_when_later_keys_dominate
+// ("Retired kernel variants").
 template <int D, bool CAUSAL, bool MASK, bool SLOW_TR>
 __device__ __forceinline__ void fwd_tile(const char* kt, const char* vt, const s16x8 (&qf)[D / 16], f32x16 (&oacc)[D / 32],
-                                          float& m_ref, float& l_run, f32x16& minit, float sc, int kv0, int len, int ql, int lane STAMP_ARGS) {
+                                          float& m_ref, float& l_run, float sc, int kv0, int len, int ql, int lane STAMP_ARGS) {
     constexpr int KS = D / 16, DT = D / 32;
-    constexpr float RESCALE_AT = 64.f;     // log2 units: P stays below 2^64, far inside fp32 / bf16 range
     static_assert(KS == 8 || KS == 4, "head_dim 128 or 64");
     constexpr int PPS = 8 / KS;            // exp pairs handled per S1 MFMA (1 for D=128, 2 for D=64)
     const int h = lane >> 5;
     f32x16 s0, s1;
     s16x8 p0a, p0b, p1a, p1b;
     const f32x2 sc2 = {sc, sc};
-    (void)sc2;
     // ---------------- block A: S0 bare, then S1 with softmax(S0) in its shadow ----------------
-#if HALVA_FWD_CINIT
-    s0 = minit, s1 = minit;
-#else
 #pragma unroll
     for (int r = 0; r < 16; ++r) s0[r] = 0.f, s1[r] = 0.f;
-#endif
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) s0 = mfma32(frag_rows<D>(kt, 0, ks, lane), qf[ks], s0);
     mask_half<MASK, CAUSAL>(s0, kv0, h, len, ql);
     STAMP(1);
     const float msub_a = (m_ref == -INFINITY) ? 0.f : m_ref;
     const f32x2 ms2a = {-msub_a, -msub_a};
-    (void)ms2a;
     f32x2 ps0 = {0.f, 0.f};
     float mx0a = -INFINITY, mx0b = -INFINITY;
     FENCE();
@@ -156,31 +86,21 @@ __device__ __forceinline__ void fwd_tile(const char* kt, const char* vt, const s
 #pragma unroll
         for (int q = 0; q < PPS; ++q) {
             const int r = 2 * (ks * PPS + q);
-#if HALVA_FWD_CINIT
-            exp_pair0(s0, r, ps0, p0a, p0b);
-#else
             exp_pair(s0, r, sc2, ms2a, ps0, p0a, p0b);
-#endif
             if (q & 1 || PPS == 1 ? (ks & 1) : false) mx0b = fmaxf(fmaxf(mx0b, s0[r]), s0[r + 1]);
             else mx0a = fmaxf(fmaxf(mx0a, s0[r]), s0[r + 1]);
         }
         FENCE();
     }
     mask_half<MASK, CAUSAL>(s1, kv0 + 32, h, len, ql);
-#ifndef HALVA_FWD_NO_PIN
     // P0 and its row sums are dead on the rare path below (which recomputes them), so LLVM sinks the whole exponential block out of
     // the S1 chain into the common successor - behind the chain, where no MFMA covers it.  Pin the values where they are produced.
     asm volatile("" : "+v"(p0a), "+v"(p0b), "+v"(ps0));
-#endif
     float sum0 = ps0[0] + ps0[1];
-#if HALVA_FWD_CINIT
-    const float tmax = xhalf_max(fmaxf(fmaxf(mx0a, mx0b), half_max(s1))) + msub_a;      // scores are relative to msub_a: back to absolute
-#else
     const float tmax = xhalf_max(fmaxf(fmaxf(mx0a, mx0b), half_max(s1))) * sc;
-#endif
     STAMP(2);
     // ---------------- rare: move the exponent reference ----------------
-    if (__any(tmax > m_ref + RESCALE_AT)) {
+    if (__any(tmax > m_ref + kRescaleAt)) {
         const float m_next = fmaxf(m_ref, tmax);
         const float alpha = (m_next == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m_ref - m_next);
         l_run *= alpha;
@@ -189,26 +109,12 @@ __device__ __forceinline__ void fwd_tile(const char* kt, const char* vt, const s
 #pragma unroll
             for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
         m_ref = m_next;
-#if HALVA_FWD_CINIT
-        // both score tiles were formed against the old reference: shift them (and every later chain's initial accumulator) to the new one
-        const float msub_n = (m_ref == -INFINITY) ? 0.f : m_ref;
-        const float adj = msub_a - msub_n;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s0[r] += adj;
-            s1[r] += adj;
-            minit[r] = -msub_n;
-        }
-        sum0 = half_exp0(s0, p0a, p0b);
-#else
         sum0 = half_exp(s0, sc, (m_ref == -INFINITY) ? 0.f : m_ref, p0a, p0b);
-#endif
     }
     STAMP(3);
     // ---------------- block B: PV(P0) with softmax(S1) in its shadow, then PV(P1) bare ----------------
     const float msub_b = (m_ref == -INFINITY) ? 0.f : m_ref;
     const f32x2 ms2b = {-msub_b, -msub_b};
-    (void)ms2b;
     f32x2 ps1 = {0.f, 0.f};
     FENCE();
 #pragma unroll
@@ -218,11 +124,7 @@ __device__ __forceinline__ void fwd_tile(const char* kt, const char* vt, const s
         FENCE();
 #pragma unroll
         for (int q = 0; q < 8 / (2 * DT); ++q) {
-#if HALVA_FWD_CINIT
-            exp_pair0(s1, 2 * (i * (8 / (2 * DT)) + q), ps1, p1a, p1b);
-#else
             exp_pair(s1, 2 * (i * (8 / (2 * DT)) + q), sc2, ms2b, ps1, p1a, p1b);
-#endif
         }
         FENCE();
     }
@@ -265,9 +167,6 @@ __device__ __forceinline__ FwdGeom fwd_geom(const SdpaParams& p, int qb, int sta
     return g;
 }
 
-#ifndef FWD_DMA
-#define FWD_DMA 1
-#endif
 // One row block.  `qf` (the Q fragments) belongs to the caller so that a block can fetch its SUCCESSOR's operands: when the tile loop
 // of a block has passed its last barrier the LDS ring is free and the Q registers are dead, so the next block's Q rows and first K/V
 // tile are requested THEN - in front of this block's store tail - instead of in the next block's prologue (measured per block,
@@ -292,7 +191,7 @@ __device__ __forceinline__ void sdpa_fwd_block(const SdpaParams& p, char* smem, 
     const bf16_t* vp = p.v + hd * D;
     bf16_t* orow = p.o + (seq_row0 + gq) * p.ld_o + hd * D;
     // K/V tiles arrive by LDS-DMA (no staging registers, no ds_write pass); the slow-transpose debug build keeps register staging
-    constexpr bool DMA = !SLOW_TR && FWD_DMA;
+    constexpr bool DMA = !SLOW_TR;
     const int wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // used for the DMA addresses only
     const int64_t krow0 = seq_row0 + start;
     auto request_q = [&](const FwdGeom& gg) {
@@ -338,13 +237,6 @@ __device__ __forceinline__ void sdpa_fwd_block(const SdpaParams& p, char* smem, 
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
     float m_ref = -INFINITY, l_run = 0.f;
     const float sc = p.scale * kLog2e;
-    f32x16 minit;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) minit[r] = 0.f;       // -m_ref, or 0 while the row has seen no key (HALVA_FWD_CINIT)
-#if HALVA_FWD_CINIT
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = scale_frag(qf[ks], sc);      // Q * scale * log2(e), once per row block
-#endif
     const bool wave_in_b = wq_min >= br.b;             // wave-uniform (br.b is a multiple of 64, strips are 32 rows)
     Stage<D, BN, NT> kst, vst;
     TileDma<D, NW> kdma, vdma;
@@ -403,9 +295,9 @@ __device__ __forceinline__ void sdpa_fwd_block(const SdpaParams& p, char* smem, 
             const int len_t = (wave_in_b && kv0 < br.a && kv0 + BN > br.a) ? br.a : len;       // tile cut at a
             if ((!CAUSAL || kv0 <= wq_max) && !hidden) {
                 if ((kv0 + BN > len_t) || (CAUSAL && kv0 + BN - 1 > wq_min))      // wave-uniform: boundary tiles only
-                    fwd_tile<D, CAUSAL, true, SLOW_TR>(kt, vt, qf, oacc, m_ref, l_run, minit, sc, kv0, len_t, ql, lane STAMP_PASS);
+                    fwd_tile<D, CAUSAL, true, SLOW_TR>(kt, vt, qf, oacc, m_ref, l_run, sc, kv0, len_t, ql, lane STAMP_PASS);
                 else
-                    fwd_tile<D, CAUSAL, false, SLOW_TR>(kt, vt, qf, oacc, m_ref, l_run, minit, sc, kv0, len_t, ql, lane STAMP_PASS);
+                    fwd_tile<D, CAUSAL, false, SLOW_TR>(kt, vt, qf, oacc, m_ref, l_run, sc, kv0, len_t, ql, lane STAMP_PASS);
             }
             if (DMA) {
                 stage_tile_dma_wait();

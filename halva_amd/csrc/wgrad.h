@@ -80,9 +80,6 @@ __device__ __forceinline__ void wgrad_dma_body(const GemmParams& p, int bx, int 
         request(it + NST - 1, (it + NST - 1) % NST);
         const char* at = a_lds + (it % NST) * TILE;
         const char* bt = b_lds + (it % NST) * TILE;
-#ifdef HALVA_WGRAD_DIAG_NOMFMA      // (timing experiment: the request path alone; results are wrong)
-        if (p.K < 0)
-#endif
 #pragma unroll
         for (int ks = 0; ks < KT / 16; ++ks) {
             s16x8 af[2], bf[2];

@@ -20,7 +20,7 @@ import torch
 
 C_OUT, F_OUT, G_OUT = 2.0, 2.0 ** -8, 2.0 ** -14      # tests/test_sdpa_rowwise_gpu.py: C_X["out"], F_X["out"], G_X["out"]
 BM, WAVE_ROWS, BN = 128, 32, 64                       # csrc/extend.hip: query rows per workgroup and per wave, keys per tile
-RESCALE_AT = 64.0                                     # log2 units (kExtRescaleAt)
+RESCALE_AT = 64.0                                     # log2 units (kRescaleAt, sdpa_common.h)
 LOG2E = 1.4426950408889634
 WIDE_PROFILES = ("up", "down", "spike_late", "spike_first", "flat")
 WIDE_SEEDS = (0, 1, 2, 3)
