@@ -5,15 +5,13 @@
 // Cache layout, per layer: K, V bf16 [B, H, Lcap, 128]; lens int32 [B] on the device (never a launch-time host value, so the step can
 // be captured in a graph later).  Slots at or beyond lens[b] are never read.
 #include "common.h"
+#include "decode_partial.h"      // kDecD / kDecChunks / kDecWaves, DecChunkRegs, decode_chunk_partial: one chunk's partial, shared with fork.hip
 #include "rope_append.h"
 #include <cmath>
 
 namespace {
 
-constexpr int kDecD = 128;          // head_dim of the LLaVA-1.5 decoder
-constexpr int kDecChunks = kDecD / 8;      // 16-byte pieces per head row
 static_assert(kDecChunks == kRopeChunks, "rope_append_row serves this head_dim");
-constexpr int kDecWaves = 4;        // waves per split-KV workgroup
 
 // ---------------------------------------------------------------------------------------------------
 // RoPE of the new token + cache append.  One workgroup per sequence b: every thread reads lens[b] before the barrier, thread 0 advances
@@ -35,107 +33,24 @@ __global__ __launch_bounds__(256) void decode_rope_append_kernel(u32x4* __restri
 // Split-KV attention, partial pass.  Workgroup (chunk c, head h, sequence b) covers keys [c KC, (c + 1) KC) ∩ [0, lens[b]); 4 waves of
 // KC / 4 keys each.  A wave takes 4 keys per step, 16 lanes per key row (one 16-byte piece of K and V per lane, straight to VGPRs - all
 // of the wave's K and V loads are issued before the first dot).  Scores in fp32 in the log2 domain (q pre-scaled by log2(e) / sqrt(D)).
-// The 4 waves combine in LDS in a fixed order; the chunk's (m, l, o[128]) go to the fp32 workspace.  Nothing here depends on B or on
-// the other rows: row b's result is bitwise the same in any batch.
+// The 4 waves combine in LDS in a fixed order; the chunk's (m, l, o[128]) go to the fp32 workspace (decode_partial.h holds the routine).
+// Nothing here depends on B or on the other rows: row b's result is bitwise the same in any batch.
 // ---------------------------------------------------------------------------------------------------
 template <int KC>
 __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const u32x4* __restrict__ q, int64_t ldq_chunks, const u32x4* __restrict__ kc,
                                                                   const u32x4* __restrict__ vc, const int32_t* __restrict__ lens, int H, int Lcap,
                                                                   int nchunk_cap, float qscale, float* __restrict__ ws_o,
                                                                   float* __restrict__ ws_ml) {
-    constexpr int NI = KC / (4 * kDecWaves);       // steps of 4 keys per wave
     const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int len = min(lens[b], Lcap);
     const int k0 = c * KC;
     if (k0 >= len) return;                         // (uniform over the workgroup: no barrier is skipped by part of it)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int sub = lane & 15, grp = lane >> 4;
+    const int sub = threadIdx.x & 15;
     const int64_t bh = (int64_t)b * H + h;
-    float qf[8];
-    unpack8(q[(int64_t)b * ldq_chunks + h * kDecChunks + sub], qf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) qf[j] *= qscale;
-    const u32x4* kb = kc + bh * Lcap * kDecChunks + sub;
-    const u32x4* vb = vc + bh * Lcap * kDecChunks + sub;
-    const int kw0 = k0 + w * (KC / kDecWaves) + grp;
-    u32x4 kr[NI], vr[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int key = kw0 + 4 * i;
-        kr[i] = key < len ? kb[(int64_t)key * kDecChunks] : u32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int key = kw0 + 4 * i;
-        vr[i] = key < len ? vb[(int64_t)key * kDecChunks] : u32x4{0, 0, 0, 0};
-    }
-    float s[NI];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        float f[8];
-        unpack8(kr[i], f);
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) d = fmaf(qf[j], f[j], d);
-        d += __shfl_xor(d, 8, 64);
-        d += __shfl_xor(d, 4, 64);
-        d += __shfl_xor(d, 2, 64);
-        d += __shfl_xor(d, 1, 64);
-        s[i] = (kw0 + 4 * i < len) ? d : -INFINITY;
-        m = fmaxf(m, s[i]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (m != -INFINITY) {                          // (a wave whose keys all lie beyond lens[b] contributes nothing)
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const float p = exp2f(s[i] - m);
-            float f[8];
-            unpack8(vr[i], f);
-            l += p;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = fmaf(p, f[j], o[j]);
-        }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        o[j] += __shfl_xor(o[j], 16, 64);
-        o[j] += __shfl_xor(o[j], 32, 64);
-    }
-    __shared__ float s_o[kDecWaves][kDecD];
-    __shared__ float s_ml[kDecWaves][2];
-    if (lane < 16) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s_o[w][sub * 8 + j] = o[j];
-    }
-    if (lane == 0) {
-        s_ml[w][0] = m;
-        s_ml[w][1] = l;
-    }
-    __syncthreads();
-    if (threadIdx.x < kDecD) {
-        const int d = threadIdx.x;
-        float M = s_ml[0][0];                      // finite: key k0 < len belongs to wave 0
-#pragma unroll
-        for (int ww = 1; ww < kDecWaves; ++ww) M = fmaxf(M, s_ml[ww][0]);
-        float acc = 0.f, L = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < kDecWaves; ++ww) {
-            const float f = s_ml[ww][0] == -INFINITY ? 0.f : exp2f(s_ml[ww][0] - M);
-            acc = fmaf(f, s_o[ww][d], acc);
-            L = fmaf(f, s_ml[ww][1], L);
-        }
-        const int64_t slot = bh * nchunk_cap + c;
-        ws_o[slot * kDecD + d] = acc;
-        if (d == 0) {
-            ws_ml[slot * 2] = M;
-            ws_ml[slot * 2 + 1] = L;
-        }
-    }
+    const u32x4 q8 = q[(int64_t)b * ldq_chunks + h * kDecChunks + sub];
+    DecChunkRegs<KC> ch;
+    ch.load(kc + bh * Lcap * kDecChunks + sub, vc + bh * Lcap * kDecChunks + sub, k0, len);
+    decode_chunk_partial<KC>(q8, ch, k0, len, qscale, ws_o, ws_ml, bh * nchunk_cap + c);
 }
 
 // Combine pass: one workgroup of 128 threads per (head, sequence) reduces the ceil(lens[b] / KC) partials in chunk order.

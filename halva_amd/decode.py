@@ -8,6 +8,9 @@ Stands in for the reference's HF `generate(..., use_cache=True)` decode path: th
 Cache layout, per layer: K, V bf16 [B, H, Lcap, D]; lens int32 [layers, B] on the device (each layer's append advances its own
 row).  Prompts are right-padded: sequence b holds positions [0, seq_len[b]).
 
+A ForkCache gives M members the rows of a parent cache as a shared prefix, read in place, and own rows behind them (n sampled answers to one
+prompt, many questions about one image): K, V bf16 [M, H, Lown, D], own_lens int32 [layers, M], prefix_lens int32 [P] as recorded at fork time.
+
 The functions below run on a DecodeStack (the Llama stack, the lm_head weight, whether the LoRA factors apply).  They also accept either
 model wrapper, which hands over its own pieces through decode_stack(): LLaVA's `.model` / `.lm_head`, VILA's `.llm.model` /
 `.llm.lm_head`.
@@ -37,6 +40,7 @@ class KVCache:
         D = cfg.hidden_size // H
         n = cfg.num_hidden_layers
         self.B, self.H, self.D, self.Lcap = B, H, D, Lcap
+        self.rope = lm.rope        # (a ForkCache whose positions outgrow cos / sin re-sizes them through it)
         self.k = [torch.empty(B, H, Lcap, D, dtype=torch.bfloat16, device=dev) for _ in range(n)]
         self.v = [torch.empty(B, H, Lcap, D, dtype=torch.bfloat16, device=dev) for _ in range(n)]
         self.lens = torch.zeros(n, B, dtype=torch.int32, device=dev)
@@ -105,26 +109,33 @@ def extend(model, cache, inputs_embeds, n_new):
     0 <= n_new[b] <= n (sequence b pushes its rows [0, n_new[b]) at positions lens[b] ..) -> logits [B, V] fp32 of each sequence's last new
     row.  A sequence with n_new[b] == 0 is left as it is (cache and lens untouched) and gets NaN logits: callers mask them.  Every check
     runs before the first launch; a block that does not fit raises RuntimeError like decode_step's."""
+    return _extend_rows(model, cache, inputs_embeds, n_new, "extend", cache.B, min(cache.Lcap, cache.cos.shape[0]), cache.Lcap,
+                        lambda layer, x, i, n_new_d, use_lora, top: layer.extend(x, cache, i, n_new_d, use_lora, top))
+
+
+def _extend_rows(model, cache, inputs_embeds, n_new, name, B, room, slots, run):
+    """The body of extend() and fork_extend(): the host checks, then run(layer, x, layer index, n_new on the device, use_lora, top rows) per
+    layer.  room: the rows the cache can hold; slots: the figure the error message names."""
     st = _stack(model)
     lm = st.lm
-    if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != cache.B:
-        raise ValueError("extend needs inputs_embeds [B=%d, n, d], got %s" % (cache.B, tuple(inputs_embeds.shape)))
+    if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != B:
+        raise ValueError("%s needs inputs_embeds [B=%d, n, d], got %s" % (name, B, tuple(inputs_embeds.shape)))
     B, n, _ = inputs_embeds.shape
     n_new = torch.as_tensor(n_new, dtype=torch.int32).view(-1).cpu()
     if n_new.numel() != B:
-        raise ValueError("extend needs one n_new per sequence (%d), got %d" % (B, n_new.numel()))
+        raise ValueError("%s needs one n_new per sequence (%d), got %d" % (name, B, n_new.numel()))
     most = int(n_new.max())
     if most < 1 or int(n_new.min()) < 0 or most > n:
-        raise ValueError("extend: every n_new[b] must lie in [0, n=%d] and one of them must be >= 1, got %s" % (n, n_new.tolist()))
-    if cache.filled + most > min(cache.Lcap, cache.cos.shape[0]):
+        raise ValueError("%s: every n_new[b] must lie in [0, n=%d] and one of them must be >= 1, got %s" % (name, n, n_new.tolist()))
+    if cache.filled + most > room:
         raise RuntimeError("KV cache full: %d slots used of %d, %d more asked for; allocate the cache for the prompt plus every new row"
-                           % (cache.filled, cache.Lcap, most))
+                           % (cache.filled, slots, most))
     cache.filled += most
     dev = lm.embed_tokens.weight.device
     n_new_d = n_new.to(dev)
     rows = (torch.arange(B, dtype=torch.int64) * n + (n_new.long() - 1).clamp_(min=0)).to(dev)
     x = inputs_embeds.to(dev, torch.bfloat16, copy=True).contiguous()      # a buffer of our own: the residual adds run on it in place
-    x = lm.each_layer(x, rows, lambda i, layer, x, top: (layer.extend(x, cache, i, n_new_d, st.use_lora, top), None))
+    x = lm.each_layer(x, rows, lambda i, layer, x, top: (run(layer, x, i, n_new_d, st.use_lora, top), None))
     return _lm_head(st, x).masked_fill_((n_new_d == 0)[:, None], float("nan"))
 
 
@@ -215,9 +226,10 @@ def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, 
     return _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)[0]
 
 
-def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix):
+def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, push=None):
     """_generate_loop's steps from a given (cache, logits [B, V]) -> (new tokens [B, n], real [B] on the device: how many of a row's n
-    tokens it selected while live, the others being pad).  The last selected token is not pushed through the model."""
+    tokens it selected while live, the others being pad).  The last selected token is not pushed through the model.  push: the function
+    that pushes a column (None = decode_step; fork_decode_step for a ForkCache)."""
     dev = logits.device
     B = logits.shape[0]
     crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
@@ -251,7 +263,7 @@ def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopp
                                    % (flags[1:].index(True), step))
             if step + 1 == max_new_tokens or flags[0]:
                 break
-        logits = decode_step(model, cache, nxt)
+        logits = (push or decode_step)(model, cache, nxt)
     return torch.stack(out, 1), real
 
 
@@ -311,6 +323,11 @@ class DecodeSession:
         self.pending = [[] for _ in self.lens]
         self.max_len = cache.Lcap
 
+    _step = None          # _loop_from's push: None = decode_step
+
+    def _extend(self, embeds, n_new):
+        return extend(self.model, self.cache, embeds, n_new)
+
     def _set_lens(self):
         cache = self.cache
         cache.lens.copy_(torch.tensor(self.lens, dtype=torch.int32).to(cache.lens.device).expand_as(cache.lens))
@@ -330,7 +347,7 @@ class DecodeSession:
         ids = torch.zeros(len(rows), n, dtype=torch.long)
         for b, r in enumerate(rows):
             ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.long)
-        lg = extend(self.model, self.cache, lm.embed_tokens(ids.to(dev)), n_new)
+        lg = self._extend(lm.embed_tokens(ids.to(dev)), n_new)
         live = torch.tensor([v > 0 for v in n_new], device=lg.device)
         self.logits = torch.where(live[:, None], lg, self.logits)
         self.lens = [a + b for a, b in zip(self.lens, n_new)]
@@ -371,7 +388,7 @@ class DecodeSession:
         B = len(self.lens)
         eos_ids, pad = eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
         select = _argmax if sampling is None else _sampler(self.model, B, dev, *sampling, generator)
-        out, real = _loop_from(self.model, self.cache, self.logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, None)
+        out, real = _loop_from(self.model, self.cache, self.logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, None, self._step)
         toks, real = out.tolist(), real.tolist()
         pushed = out.shape[1] - 1                       # every column but the last went through decode_step
         for b in range(B):
@@ -380,3 +397,142 @@ class DecodeSession:
             self.pending[b] = toks[b][held:real[b]]
         self._set_lens()
         return out
+
+    @torch.no_grad()
+    def fork(self, n=None, prefix_of=None, max_new=256):
+        """Branch the session: -> ForkedSession whose members continue from this session's rows without copying them.  n: every row n ways
+        (member b * n + i continues row b); prefix_of: the general form, a non-decreasing list of this session's row indices, one per
+        member.  max_new: the own rows each member can hold (tokens generated plus ids appended).  Pending tokens are pushed first, so the
+        kept logits match the cache; member m starts from logits[prefix_of[m]].  This session may go on appending and generating while its
+        forks live: they read its cache only below the lengths recorded here."""
+        if (n is None) == (prefix_of is None):
+            raise ValueError("session.fork needs n or prefix_of (one of them)")
+        if n is not None:
+            if int(n) < 1:
+                raise ValueError("session.fork: n=%r (needs an int >= 1)" % (n,))
+            prefix_of = [b for b in range(len(self.lens)) for _ in range(int(n))]
+        prefix_of = check_prefix_of(prefix_of, len(self.lens))
+        if max_new is None or int(max_new) < 1:
+            raise ValueError("session.fork: max_new=%r (needs an int >= 1)" % (max_new,))
+        self._push([[] for _ in self.lens])
+        fork = ForkCache(self.cache, prefix_of, int(max_new), self.lens)
+        logits = self.logits[torch.tensor(prefix_of, dtype=torch.long, device=self.logits.device)]
+        return ForkedSession(self.model, fork, logits, self.config)
+
+
+# ------------------------------------------------------------------------------------------------
+# forks: M members over the rows of a parent cache
+def check_prefix_of(prefix_of, P):
+    """-> prefix_of as a list of ints: one parent row index in [0, P) per member, non-decreasing (members of one row are contiguous)."""
+    try:
+        out = [int(v) for v in prefix_of]
+    except TypeError:
+        raise ValueError("prefix_of must be a list of ints, got %r" % (prefix_of,))
+    if not out:
+        raise ValueError("prefix_of is empty: a fork needs at least one member")
+    if min(out) < 0 or max(out) >= P:
+        raise ValueError("prefix_of holds row indices in [0, %d), got %s" % (P, out))
+    if any(a > b for a, b in zip(out, out[1:])):
+        raise ValueError("prefix_of must be non-decreasing (members of one prefix row are contiguous), got %s" % out)
+    return out
+
+
+class ForkCache:
+    """M members over the rows of `parent` (a KVCache): member m reads parent row prefix_of[m] in place up to prefix_lens[prefix_of[m]] - the
+    rows that row held at fork time (a host list; None = read parent.lens) - and owns k, v bf16 [M, H, Lown, D] per layer behind it, with
+    own_lens int32 [layers, M] on the device.  Own row t of member m sits at position prefix_lens[prefix_of[m]] + t.  Nothing is copied
+    from the parent, and its slots at or beyond the recorded lengths are never read: it may go on appending while forks live."""
+
+    def __init__(self, parent, prefix_of, Lown, prefix_lens=None):
+        prefix_of = check_prefix_of(prefix_of, parent.B)
+        if int(Lown) < 1:
+            raise ValueError("a fork needs Lown >= 1 own slots, got %r" % (Lown,))
+        lens = parent.lens[0].tolist() if prefix_lens is None else [int(v) for v in prefix_lens]
+        if len(lens) != parent.B:
+            raise ValueError("prefix_lens needs one length per parent row (%d), got %d" % (parent.B, len(lens)))
+        used = sorted(set(prefix_of))
+        if any(lens[p] < 1 or lens[p] > parent.Lcap for p in used):
+            raise ValueError("every forked row needs between 1 and %d rows in the parent, got %s" % (parent.Lcap, [lens[p] for p in used]))
+        dev = parent.k[0].device
+        n = len(parent.k)
+        M, H, D = len(prefix_of), parent.H, parent.D
+        self.parent, self.M, self.P, self.H, self.D, self.Lown = parent, M, parent.B, H, D, int(Lown)
+        self.host_prefix_of, self.host_prefix_lens = prefix_of, lens
+        self.prefix_of = torch.tensor(prefix_of, dtype=torch.int32, device=dev)
+        self.prefix_lens = torch.tensor(lens, dtype=torch.int32, device=dev)
+        self.k = [torch.empty(M, H, self.Lown, D, dtype=torch.bfloat16, device=dev) for _ in range(n)]
+        self.v = [torch.empty(M, H, self.Lown, D, dtype=torch.bfloat16, device=dev) for _ in range(n)]
+        self.own_lens = torch.zeros(n, M, dtype=torch.int32, device=dev)
+        self.filled = 0            # host-side upper bound of max_m own_lens[m], as KVCache.filled
+        self.ws = torch.empty(max(K.fork_ws_bytes(M, H, parent.Lcap, self.Lown), 16), dtype=torch.uint8, device=dev)
+        need = max(lens[p] for p in used) + self.Lown
+        cos, sin = parent.cos, parent.sin
+        if cos.shape[0] < need:
+            cos, sin = parent.rope(need, dev)
+        if cos.shape[0] < need:
+            # the append kernels skip a row whose position lies beyond the tables, and the attention would then run without it
+            raise RuntimeError("RoPE tables of %d rows do not cover the fork's %d positions" % (cos.shape[0], need))
+        self.cos, self.sin = cos, sin
+
+    # what DecodeSession asks of its cache
+    lens = property(lambda self: self.own_lens)
+    Lcap = property(lambda self: self.Lown)
+
+
+@torch.no_grad()
+def fork_decode_step(model, fork, token_ids):
+    """decode_step for the members of a ForkCache: token_ids [M] -> logits [M, V] fp32.  Appends each layer's k / v at own slot own_lens[m]."""
+    if fork.filled >= fork.Lown:
+        raise RuntimeError("KV cache full: %d own slots used of %d; fork with max_new for every new token" % (fork.filled, fork.Lown))
+    fork.filled += 1
+    st = _stack(model)
+    lm = st.lm
+    x = lm.embed_tokens(token_ids.to(lm.embed_tokens.weight.device).long())          # a fresh buffer: the residual adds run on it in place
+    x = lm.each_layer(x, None, lambda i, layer, x, top: (layer.fork_decode(x, fork, i, st.use_lora), None))
+    return _lm_head(st, x)
+
+
+@torch.no_grad()
+def fork_extend(model, fork, inputs_embeds, n_new):
+    """extend for the members of a ForkCache: inputs_embeds [M, n, d], n_new [M] host ints -> logits [M, V] fp32 of each member's last new
+    row (NaN where n_new[m] == 0), every check before the first launch."""
+    return _extend_rows(model, fork, inputs_embeds, n_new, "fork_extend", fork.M, fork.Lown, fork.Lown,
+                        lambda layer, x, i, n_new_d, use_lora, top: layer.fork_extend(x, fork, i, n_new_d, use_lora, top))
+
+
+@torch.no_grad()
+def sample_fork(model, inputs_embeds, seq_len, n, max_new_tokens, eos_ids, pad, temperature, top_k, top_p, generator=None,
+                stopping_criteria=None, prefix=None, prefill_chunk=None):
+    """sample() with n continuations per prompt (generate's num_return_sequences): ONE prompt pass at batch B into a cache of the prompt's
+    rows, a fork n ways, and the sampled loop on the B * n members (member b * n + i continues prompt b) -> LongTensor [B * n, len].  Each
+    step draws u = torch.rand(B * n, generator=generator) exactly once, done members included."""
+    B, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
+    select = _sampler(model, B * n, inputs_embeds.device, temperature, top_k, top_p, generator)
+    cache = KVCache(model, B, T, inputs_embeds.device)
+    if prefill_chunk is None:
+        logits = prefill(model, inputs_embeds, seq_len, cache)
+    else:
+        logits = prefill_chunked(model, inputs_embeds, seq_len, cache, prefill_chunk)
+    prefix_of = [b for b in range(B) for _ in range(n)]
+    fork = ForkCache(cache, prefix_of, max_new_tokens, [int(v) for v in seq_len])
+    logits = logits[torch.tensor(prefix_of, dtype=torch.long, device=logits.device)]
+    return _loop_from(model, fork, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, fork_decode_step)[0]
+
+
+class ForkedSession(DecodeSession):
+    """The members of DecodeSession.fork(): generate() and append() with DecodeSession's signatures and rules, on a ForkCache.  lens[m] counts
+    the member's OWN rows (max_len = the fork's max_new); member m's history is row prefix_of[m] of the parent up to prefix_lens[m] and
+    then its own rows."""
+
+    def __init__(self, model, fork, logits, config=None):
+        super().__init__(model, fork, logits, [0] * fork.M, config)
+        self.prefix_of = list(fork.host_prefix_of)
+        self.prefix_lens = [fork.host_prefix_lens[p] for p in self.prefix_of]
+
+    _step = staticmethod(lambda model, fork, tok: fork_decode_step(model, fork, tok))
+
+    def _extend(self, embeds, n_new):
+        return fork_extend(self.model, self.cache, embeds, n_new)
+
+    def fork(self, n=None, prefix_of=None, max_new=256):
+        raise NotImplementedError("forks of forks are not implemented; fork the parent session again")

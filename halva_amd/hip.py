@@ -67,6 +67,10 @@ SIGNATURES = {
     "halva_extend_rope_append": [_P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "halva_extend_attn": [_P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "halva_extend_advance": [_P, _P, _I, _I, _P],
+    "halva_fork_rope_append": [_P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "halva_fork_decode_attn": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P],
+    "halva_fork_extend_rope_append": [_P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "halva_fork_extend_attn": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "halva_sample_top_k_top_p": [_P, _L, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P],
     "halva_sample_max_vocab": [],
 }
@@ -112,6 +116,8 @@ def load():
     lib.halva_decode_attn_ws_bytes.argtypes = [c_int, c_int, c_int]
     lib.halva_extend_attn_ws_bytes.restype = c_int64
     lib.halva_extend_attn_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.halva_fork_decode_attn_ws_bytes.restype = c_int64
+    lib.halva_fork_decode_attn_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
     _lib = lib
     return lib
 

@@ -346,6 +346,67 @@ def extend_advance(lens, n_new, Lcap):
     return lens
 
 
+# forks of a kept cache (halva_amd/decode.py:ForkCache): the parent's rows read in place, own rows behind them
+def fork_ws_bytes(M, H, Lpre, Lown):
+    """Workspace bytes of fork_decode_attention (halva_fork_decode_attn_ws_bytes; 0 for bad sizes)."""
+    return int(hip.load().halva_fork_decode_attn_ws_bytes(M, H, Lpre, Lown))
+
+
+def _chk_fork(prefix_lens, prefix_of, own_lens):
+    _chk(prefix_lens, torch.int32, "prefix_lens"), _chk(prefix_of, torch.int32, "prefix_of"), _chk(own_lens, torch.int32, "own_lens")
+
+
+def fork_rope_append(qkv, cos, sin, prefix_lens, prefix_of, kown, vown, own_lens, H, D):
+    """qkv [M, 3*H*D] (new tokens): q rotated in place at position prefix_lens[prefix_of[m]] + own_lens[m], rotated k / plain v written to
+    own slot own_lens[m] of the [M, H, Lown, D] caches, own_lens[m] += 1 (halva_fork_rope_append)."""
+    _chk(qkv, torch.bfloat16, "qkv"), _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown")
+    _chk_fork(prefix_lens, prefix_of, own_lens)
+    call("halva_fork_rope_append", ptr(qkv), qkv.shape[-1], ptr(cos), ptr(sin), cos.shape[0], ptr(prefix_lens), ptr(prefix_of), ptr(kown),
+         ptr(vown), ptr(own_lens), qkv.shape[0], prefix_lens.shape[0], H, D, kown.shape[2], stream_ptr())
+    return qkv
+
+
+def fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, ws, H, D, out_width=None, ldq=None):
+    """One query row per (member, head) over the parent keys [0, prefix_lens[p]) of row p = prefix_of[m] (pk, pv [Bp, H, Lpre, D], read in
+    place) and then the own keys [0, own_lens[m]) (kown, vown [M, H, Lown, D]) -> bf16 [M, out_width] (halva_fork_decode_attn)."""
+    _chk(q, torch.bfloat16, "q"), _chk(pk, torch.bfloat16, "pk"), _chk(pv, torch.bfloat16, "pv")
+    _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown")
+    _chk_fork(prefix_lens, prefix_of, own_lens)
+    M = q.shape[0]
+    width = out_width or H * D
+    out = torch.empty(M, width, dtype=torch.bfloat16, device=q.device)
+    call("halva_fork_decode_attn", ptr(q), ldq or q.shape[-1], ptr(pk), ptr(pv), ptr(prefix_lens), ptr(prefix_of), ptr(kown), ptr(vown),
+         ptr(own_lens), ptr(out), width, ptr(ws), ws.numel() * ws.element_size(), M, prefix_lens.shape[0], H, D, pk.shape[2], kown.shape[2], 0.0,
+         stream_ptr())
+    return out
+
+
+def fork_extend_rope_append(qkv, cos, sin, prefix_lens, prefix_of, kown, vown, own_lens, n_new, H, D):
+    """qkv [M, n, 3*H*D]: extend_rope_append on the own caches with row i of member m at position prefix_lens[prefix_of[m]] + own_lens[m] + i;
+    own_lens is NOT advanced (halva_fork_extend_rope_append)."""
+    _chk(qkv, torch.bfloat16, "qkv"), _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown")
+    _chk_fork(prefix_lens, prefix_of, own_lens), _chk(n_new, torch.int32, "n_new")
+    M, n, ld = qkv.shape
+    call("halva_fork_extend_rope_append", ptr(qkv), ld, n * ld, ptr(cos), ptr(sin), cos.shape[0], ptr(prefix_lens), ptr(prefix_of), ptr(kown),
+         ptr(vown), ptr(own_lens), ptr(n_new), M, n, prefix_lens.shape[0], H, D, kown.shape[2], stream_ptr())
+    return qkv
+
+
+def fork_extend_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, n_new, H, D, out_width=None, out=None):
+    """extend_attention with the prefix row's keys in front of the own ones -> bf16 [M, n, out_width] (halva_fork_extend_attn).  Runs behind
+    fork_extend_rope_append and before extend_advance(own_lens, n_new, Lown)."""
+    _chk(q, torch.bfloat16, "q"), _chk(pk, torch.bfloat16, "pk"), _chk(pv, torch.bfloat16, "pv")
+    _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown")
+    _chk_fork(prefix_lens, prefix_of, own_lens), _chk(n_new, torch.int32, "n_new")
+    M, n, ldq = q.shape
+    width = out_width or H * D
+    if out is None:
+        out = torch.zeros(M, n, width, dtype=torch.bfloat16, device=q.device)
+    call("halva_fork_extend_attn", ptr(q), ldq, n * ldq, ptr(pk), ptr(pv), ptr(prefix_lens), ptr(prefix_of), ptr(kown), ptr(vown), ptr(own_lens),
+         ptr(n_new), ptr(out), width, n * width, M, n, prefix_lens.shape[0], H, D, pk.shape[2], kown.shape[2], 0.0, stream_ptr())
+    return out
+
+
 def sample_max_vocab():
     """The widest row sample_top_k_top_p takes (a library constant)."""
     return int(hip.load().halva_sample_max_vocab())

@@ -448,6 +448,29 @@ class DecoderLayer(nn.Module):
             return a
         return self._block(x, attend, use_lora, True, rows)
 
+    def fork_decode(self, x, fork, layer_idx, use_lora=True):
+        """decode() for the members of a ForkCache (halva_amd/decode.py): x [M, d]; the new row is appended to the member's own rows and
+        attends the parent's prefix row, read in place, followed by the own rows."""
+        pk, pv = fork.parent.k[layer_idx], fork.parent.v[layer_idx]
+        kc, vc, lens = fork.k[layer_idx], fork.v[layer_idx], fork.own_lens[layer_idx]
+
+        def attend(qkv):
+            K.fork_rope_append(qkv, fork.cos, fork.sin, fork.prefix_lens, fork.prefix_of, kc, vc, lens, self.H, self.D)
+            return K.fork_decode_attention(qkv, pk, pv, fork.prefix_lens, fork.prefix_of, kc, vc, lens, fork.ws, self.H, self.D, self.o.in_width)
+        return self._block(x, attend, use_lora, True, None)
+
+    def fork_extend(self, x, fork, layer_idx, n_new_d, use_lora=True, rows=None):
+        """extend() for the members of a ForkCache: x [M, n, d], rows and return as there."""
+        pk, pv = fork.parent.k[layer_idx], fork.parent.v[layer_idx]
+        kc, vc, lens = fork.k[layer_idx], fork.v[layer_idx], fork.own_lens[layer_idx]
+
+        def attend(qkv):
+            K.fork_extend_rope_append(qkv, fork.cos, fork.sin, fork.prefix_lens, fork.prefix_of, kc, vc, lens, n_new_d, self.H, self.D)
+            a = K.fork_extend_attention(qkv, pk, pv, fork.prefix_lens, fork.prefix_of, kc, vc, lens, n_new_d, self.H, self.D, self.o.in_width)
+            K.extend_advance(lens, n_new_d, fork.Lown)
+            return a
+        return self._block(x, attend, use_lora, True, rows)
+
     def _block(self, x, attend, use_lora, own_x, rows):
         """The decoder block, written once for forward(), decode() and extend(): attend(qkv) -> a [.., o.in_width] is all that differs."""
         # every producer kernel writes straight into the (wider) operand buffer of the projection that follows it

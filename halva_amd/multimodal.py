@@ -216,18 +216,29 @@ class MultimodalMixin:
 
     @torch.no_grad()
     def _generate(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None, prefill_chunk=None):
+                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None, prefill_chunk=None, num_return_sequences=1):
         """The body of `generate`: _embed_prompt, then halva_amd/decode.py:greedy, or :sample when do_sample is set.  prefill_chunk: None =
-        one prompt pass; an int >= 1 = the prompt pass in blocks of that many rows (decode.prefill_chunked)."""
+        one prompt pass; an int >= 1 = the prompt pass in blocks of that many rows (decode.prefill_chunked).  num_return_sequences = n > 1
+        (sampling only, as in HF): one prompt pass, then n continuations per prompt over a forked cache (decode.sample_fork) -> rows
+        b * n + i, with the prompt repeated where the prompt is returned."""
         from . import decode as DEC
         sampling = DEC.check_generate_args(num_beams, do_sample, max_new_tokens, temperature, top_k, top_p)
+        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        if n_ret < 1:
+            raise ValueError("generate: num_return_sequences=%r (needs an int >= 1)" % (num_return_sequences,))
+        if n_ret > 1 and sampling is None:
+            raise ValueError("generate: num_return_sequences=%d needs do_sample=True: greedy decoding returns one sequence per prompt" % n_ret)
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("generate: prefill_chunk=%r (needs an int >= 1, or None)" % (prefill_chunk,))
         embeds, seq_len = self._embed_prompt(input_ids, images, attention_mask)
         dev = self.device
         eos_ids, pad = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, dev)
         prompt = input_ids.to(dev) if self.generate_returns_prompt else None
-        if sampling is None:
+        if n_ret > 1:
+            prompt = None if prompt is None else prompt.repeat_interleave(n_ret, 0)
+            out = DEC.sample_fork(self, embeds, seq_len, n_ret, max_new_tokens, eos_ids, pad, *sampling, generator=generator,
+                                  stopping_criteria=stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
+        elif sampling is None:
             out = DEC.greedy(self, embeds, seq_len, max_new_tokens, eos_ids, pad, stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
         else:
             out = DEC.sample(self, embeds, seq_len, max_new_tokens, eos_ids, pad, *sampling, generator=generator,

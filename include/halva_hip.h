@@ -344,6 +344,42 @@ int64_t halva_extend_attn_ws_bytes(int B, int n, int H, int Lcap);
 /* lens[b] = min(lens[b] + n_new[b], Lcap): a launch of its own behind the attention. */
 int halva_extend_advance(int32_t* lens, const int32_t* n_new, int B, int Lcap, void* stream);
 
+/* ---- Forks of a kept cache (halva_amd/decode.py:ForkCache - n continuations over one shared prompt, many questions about one image; no
+ * reference counterpart: HF repeats the prompt's cache per returned sequence).  M members read P prefix rows of a parent cache
+ * pk, pv bf16 [Bp, H, Lpre, D] in place and own kown, vown bf16 [M, H, Lown, D], D = 128.  prefix_of int32 [M]: the parent row of each member,
+ * non-decreasing (members of one row are contiguous), values in [0, P); prefix_lens int32 [P]: the rows of each prefix, recorded at fork
+ * time; own_lens int32 [M].  All of them live on the device.  Own row t of member m sits at position prefix_lens[prefix_of[m]] + t.  Parent
+ * slots at or beyond prefix_lens[p] and own slots at or beyond own_lens[m] are never read; nothing is copied from the parent.
+ *
+ * RoPE + append of one new row per member: halva_decode_rope_append (the same routine) with the row rotated at position
+ * prefix_lens[prefix_of[m]] + own_lens[m] and written to own slot own_lens[m]; own_lens[m] += 1.  A full own cache, or a position at or
+ * beyond max_pos, leaves member m untouched. */
+int halva_fork_rope_append(void* qkv, int64_t ldqkv, const void* cos, const void* sin, int max_pos, const int32_t* prefix_lens,
+                           const int32_t* prefix_of, void* kown, void* vown, int32_t* own_lens, int M, int P, int H, int D, int Lown,
+                           void* stream);
+/* Single-query attention of member m over parent keys [0, prefix_lens[p]) of row p = prefix_of[m] followed by its own keys
+ * [0, own_lens[m]).  Split-KV with 256-key chunks: a prefix pass (one workgroup per chunk, head, prefix row and block of up to 16 members
+ * loads the chunk's K and V once and serves every member of the block from it), an own pass (halva_decode_attn's partial pass over the own
+ * rows, chunked from own key 0) and a combine pass over ceil(prefix_lens / 256) + ceil(own_lens / 256) partials in that order.  No float
+ * atomics; one reduction order fixed by (prefix_lens[p], own_lens[m]) alone: member m's bits do not depend on M, on the other members, on
+ * its place in a block or on other prefix rows.  own_lens[m] = 0 is attention over the prefix alone.  Unused workspace is never read.
+ * scale = 1/sqrt(D) when <= 0.  ws_bytes >= halva_fork_decode_attn_ws_bytes(M, H, Lpre, Lown) (0 for bad sizes). */
+int halva_fork_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens, const int32_t* prefix_of,
+                           const void* kown, const void* vown, const int32_t* own_lens, void* out, int64_t ld_out, void* ws, int64_t ws_bytes,
+                           int M, int P, int H, int D, int Lpre, int Lown, float scale, void* stream);
+int64_t halva_fork_decode_attn_ws_bytes(int M, int H, int Lpre, int Lown);
+/* Up to n rows per member: halva_extend_rope_append and halva_extend_attn with the prefix in front.  Row i < n_new[m] goes to own slot
+ * own_lens[m] + i at position prefix_lens[p] + own_lens[m] + i; the attention walks the 64-key tiles of the prefix row first (all visible,
+ * the last one masked at prefix_lens[p]; the exponent reference starts there) and then the own tiles exactly as halva_extend_attn does with
+ * past = own_lens[m] - one kernel body, one tile loop.  Row (m, i)'s bits do not depend on the other members or their n_new.  The prefix
+ * read is not shared between members here.  halva_extend_advance(own_lens, n_new, M, Lown) follows. */
+int halva_fork_extend_rope_append(void* qkv, int64_t ldrow, int64_t ldseq, const void* cos, const void* sin, int max_pos,
+                                  const int32_t* prefix_lens, const int32_t* prefix_of, void* kown, void* vown, const int32_t* own_lens,
+                                  const int32_t* n_new, int M, int n, int P, int H, int D, int Lown, void* stream);
+int halva_fork_extend_attn(const void* q, int64_t ldrow, int64_t ldseq, const void* pk, const void* pv, const int32_t* prefix_lens,
+                           const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, const int32_t* n_new, void* out,
+                           int64_t ld_out_row, int64_t ld_out_seq, int M, int n, int P, int H, int D, int Lpre, int Lown, float scale, void* stream);
+
 /* ---- Sampling (generate with do_sample=True, halva_amd/decode.py:sample).  replaces what HF's generate runs per step behind the reference's
  * `model.generate(..., do_sample=True, temperature=args.temperature, top_p=args.top_p, ...)` (eval_hall/model_chair_loader.py:124-130):
  * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper(min_tokens_to_keep=1) -> softmax -> torch.multinomial, i.e. about ten

@@ -20,7 +20,13 @@ past = 0, n = 639 beside halva_sdpa_causal_fwd_ld on the same rows (the prompt p
 n = 32, and - with the model - ms of a second turn of 32 ids through session.append beside a fresh start_session (vision tower, splice,
 prompt pass) on the concatenated prompt.  Measurement only, no gate.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--out profiles/r07_decode.json] [--steps 32]
+--fork: the record gains `fork` (7B geometry, H = 32, 16 members).  `attention`: us, bytes moved and TB/s of halva_fork_decode_attn at
+prefix 2048 and at prefix 639, own = 32, beside halva_decode_attn on 16 materialised caches of the same logical keys, the two timed
+alternately in one process and their outputs compared.  With the model: `sampled_loop`, generate's num_return_sequences=16 path
+(decode.sample_fork) beside decode.sample on the prompt repeated 16 times - ms/step, prefill ms, cache GB; `questions`, 16 questions of 32
+ids forked from one 639-row prompt and appended beside a fresh B = 16 start_session on the concatenated prompts.  Measurement only, no gate.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--fork] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -251,6 +257,122 @@ def extend_turn_numbers(m, text=64, image=336, turn=32):
     return res
 
 
+FORK_N, FORK_OWN = 16, 32
+
+
+def fork_attn_bytes(prefix, own, n, H, D=128):
+    """K and V bytes the two attentions have to read for n members of `prefix` shared and `own` private bf16 key rows each: (the fork:
+    the prefix once per block of 16 members, the own rows per member; n materialised caches: everything per member)."""
+    row = 2 * H * D * 2
+    return (-(-n // 16) * prefix + n * own) * row, n * (prefix + own) * row
+
+
+def fork_kernel_numbers(H=32, D=128, reps=50, rounds=3):
+    from halva_amd import kernels as K
+    dev = "cuda"
+    n, own = FORK_N, FORK_OWN
+    res = {}
+    for prefix in (2048, 639):
+        Lown = 2 * own
+        pk = torch.randn(1, H, prefix, D, device=dev).to(torch.bfloat16)
+        pv = torch.randn(1, H, prefix, D, device=dev).to(torch.bfloat16)
+        kc = torch.randn(n, H, Lown, D, device=dev).to(torch.bfloat16)
+        vc = torch.randn(n, H, Lown, D, device=dev).to(torch.bfloat16)
+        q = torch.randn(n, 3 * H * D, device=dev).to(torch.bfloat16)
+        plens = torch.tensor([prefix], dtype=torch.int32, device=dev)
+        of = torch.zeros(n, dtype=torch.int32, device=dev)
+        olens = torch.full((n,), own, dtype=torch.int32, device=dev)
+        ws = torch.empty(K.fork_ws_bytes(n, H, prefix, Lown), dtype=torch.uint8, device=dev)
+        # the same logical keys as n caches of their own
+        L = prefix + own
+        km = torch.cat([pk.expand(n, -1, -1, -1), kc[:, :, :own]], 2).contiguous()
+        vm = torch.cat([pv.expand(n, -1, -1, -1), vc[:, :, :own]], 2).contiguous()
+        lens = torch.full((n,), L, dtype=torch.int32, device=dev)
+        ws1 = torch.empty(K.decode_ws_bytes(n, H, L), dtype=torch.uint8, device=dev)
+        fork = lambda: K.fork_decode_attention(q, pk, pv, plens, of, kc, vc, olens, ws, H, D)      # noqa: E731
+        flat = lambda: K.decode_attention(q, km, vm, lens, ws1, H, D)                                # noqa: E731
+        diff = float((fork().float() - flat().float()).abs().max())
+        tf, tm = [], []
+        for _ in range(rounds):                   # alternately: other work shares the machine
+            tf.append(_time(fork, reps, warmup=5))
+            tm.append(_time(flat, reps, warmup=5))
+        bf, bm = fork_attn_bytes(prefix, own, n, H, D)
+        f_ms, m_ms = statistics.median(tf), statistics.median(tm)
+        res["prefix%d" % prefix] = {
+            "members": n, "own": own, "max_abs_diff": diff,
+            "fork": {"us": round(f_ms * 1e3, 2), "bytes": bf, "TB_s": round(bf / (f_ms * 1e-3) / 1e12, 3), "us_rounds": [round(t * 1e3, 2) for t in tf]},
+            "materialised": {"us": round(m_ms * 1e3, 2), "bytes": bm, "TB_s": round(bm / (m_ms * 1e-3) / 1e12, 3),
+                             "us_rounds": [round(t * 1e3, 2) for t in tm]}}
+    return res
+
+
+def _cache_gb(m, rows):
+    cfg = m.decode_stack().lm.config
+    return round(cfg.num_hidden_layers * 2 * rows * cfg.hidden_size * 2 / 1e9, 3)
+
+
+def fork_loop_numbers(m, steps, text=64, image=336):
+    """The sampled loop with 16 continuations of one prompt: one prompt pass and a fork, beside the prompt repeated 16 times."""
+    import time
+    from halva_amd import decode as DEC
+    g = torch.Generator().manual_seed(0)
+    T_, k, p = SAMPLE_SETTINGS[0]
+    n = FORK_N
+    none = torch.empty(0, dtype=torch.long, device="cuda")
+    ids = torch.randint(3, 32000, (1, text), generator=g)
+    ids[:, 0] = 1
+    ids[:, 6] = -200
+    images = torch.randn(1, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+    with torch.no_grad():
+        e1, plan1 = m._splice(ids.cuda(), None, None, None, images)
+        e16, plan16 = m._splice(ids.repeat(n, 1).cuda(), None, None, None, images.repeat(n, 1, 1, 1))
+    T = e1.shape[1]
+
+    def wall(fn, cnt):
+        best = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(cnt)
+            torch.cuda.synchronize()
+            best.append(time.perf_counter() - t0)
+        return statistics.median(best) * 1e3
+
+    def forked(cnt):
+        DEC.sample_fork(m, e1, plan1.seq_len, n, cnt, none, 0, T_, k, p)
+
+    def repeated(cnt):
+        DEC.sample(m, e16, plan16.seq_len, cnt, none, 0, T_, k, p)
+    forked(2), repeated(2)
+    with torch.no_grad():
+        pre1 = _time(lambda: DEC.prefill(m, e1, plan1.seq_len, DEC.KVCache(m, 1, T)), 3, warmup=1)
+        pre16 = _time(lambda: DEC.prefill(m, e16, plan16.seq_len, DEC.KVCache(m, n, T + steps + 1)), 3, warmup=1)
+    return {"prompt_rows": T, "members": n, "steps": steps, "temperature": T_, "top_k": k, "top_p": p,
+            "fork": {"ms_per_step": round((wall(forked, steps + 1) - wall(forked, 1)) / steps, 3), "prefill_ms": round(pre1, 2),
+                     "cache_GB": _cache_gb(m, T + n * (steps + 1))},
+            "repeated_prompt": {"ms_per_step": round((wall(repeated, steps + 1) - wall(repeated, 1)) / steps, 3), "prefill_ms": round(pre16, 2),
+                                "cache_GB": _cache_gb(m, n * (T + steps + 1))}}
+
+
+def fork_question_numbers(m, text=64, image=336, turn=32):
+    """16 questions of `turn` ids about one image: forked from one session and appended, beside a fresh B = 16 start_session."""
+    g = torch.Generator().manual_seed(0)
+    n = FORK_N
+    ids = torch.randint(3, 32000, (1, text), generator=g)
+    ids[:, 0] = 1
+    ids[:, 6] = -200
+    more = torch.randint(3, 32000, (n, turn), generator=g)
+    images = torch.randn(1, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+    ses = m.start_session(ids, images=images, max_len=text + 1024)
+
+    def forked():
+        ses.fork(n, max_new=2 * turn).append(more)
+    both, images16 = torch.cat([ids.repeat(n, 1), more], 1), images.repeat(n, 1, 1, 1)
+    f_ms = _time(forked, 3, warmup=1)
+    fresh_ms = _time(lambda: m.start_session(both, images=images16, max_len=text + turn + 1024), 3, warmup=1)
+    return {"prompt_rows": ses.lens[0], "questions": n, "turn_ids": turn, "fork_append_ms": round(f_ms, 2), "fresh_prefill_ms": round(fresh_ms, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -260,6 +382,9 @@ def main():
     ap.add_argument("--merged", action="store_true", help="also time the decode step after merge_and_unload() on the same model")
     ap.add_argument("--sample", action="store_true", help="also time the native token select, its torch composition and the sampled loop")
     ap.add_argument("--extend", action="store_true", help="also time the extend attention beside the prompt pass's, and a session's second turn")
+    ap.add_argument("--fork", action="store_true",
+                    help="also time the fork decode attention beside 16 materialised caches, the num_return_sequences=16 loop beside the "
+                         "repeated prompt, and 16 forked questions beside a fresh prefill")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
@@ -271,6 +396,8 @@ def main():
         rec["sample"] = select_numbers()
     if a.extend:
         rec["extend"] = extend_kernel_numbers()
+    if a.fork:
+        rec["fork"] = {"attention": fork_kernel_numbers(H=40 if vila else 32)}
     if not a.skip_model:
         m = model_vila13b() if vila else model_7b()
         def weights_gb():
@@ -284,6 +411,9 @@ def main():
             rec["sample"].update(loop_numbers(m, a.steps, text=60, image=384) if vila else loop_numbers(m, a.steps))
         if a.extend:
             rec["extend"]["second_turn"] = extend_turn_numbers(m, text=60, image=384) if vila else extend_turn_numbers(m)
+        if a.fork:
+            rec["fork"]["sampled_loop"] = fork_loop_numbers(m, a.steps, text=60, image=384) if vila else fork_loop_numbers(m, a.steps)
+            rec["fork"]["questions"] = fork_question_numbers(m, text=60, image=384) if vila else fork_question_numbers(m)
         if a.merged:
             import time
             torch.cuda.synchronize()
