@@ -31,6 +31,30 @@ struct DecChunkRegs {
             vr[i] = key < len ? vb[(int64_t)key * kDecChunks] : u32x4{0, 0, 0, 0};
         }
     }
+    // As load(), with key t of the (member, head) row fetched from the slot of ANOTHER member: anc_row[t] names the member whose own slot t
+    // holds the row (beam search's ancestry table, fork.hip:beam_own_partial_kernel).  kbase / vbase: the [M, H, Lown, 128] caches + this
+    // lane's piece.  The 16 lanes of a key row read the same word of anc_row; the lane's NI words are loaded first, then all K, then all V.
+    // The member index is clamped into [0, M): whatever the table holds, no address leaves the allocation.
+    __device__ __forceinline__ void load_via(const u32x4* __restrict__ kbase, const u32x4* __restrict__ vbase, const int32_t* __restrict__ anc_row,
+                                             int h, int H, int Lown, int M, int k0, int len) {
+        const int kw0 = first_key(k0);
+        int src[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int key = kw0 + 4 * i;
+            src[i] = key < len ? min(max(anc_row[key], 0), M - 1) : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int key = kw0 + 4 * i;
+            kr[i] = key < len ? kbase[(((int64_t)src[i] * H + h) * Lown + key) * kDecChunks] : u32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int key = kw0 + 4 * i;
+            vr[i] = key < len ? vbase[(((int64_t)src[i] * H + h) * Lown + key) * kDecChunks] : u32x4{0, 0, 0, 0};
+        }
+    }
     static __device__ __forceinline__ int first_key(int k0) {
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         return k0 + w * (KC / kDecWaves) + (lane >> 4);

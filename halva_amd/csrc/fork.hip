@@ -14,6 +14,11 @@
 // own_lens[m]) alone: its bits do not depend on M, on the other members, on its place in a block of 16 or on other prefix rows.
 //
 // Pushing n rows per member: extend.hip's two kernels with the prefix in front (extend_attn.h's body with its prefix phase on).
+//
+// Beam search (halva_amd/decode.py:BeamCache): the members are B prompts x K beams, and a beam that continues another beam's history moves
+// no K / V row - an ancestry table anc int32 [M, Lown] names, per member and own row, the member whose slot holds it.  halva_beam_decode_attn
+// is the decode step's three launches with the own pass reading through the table (beam_own_partial_kernel); halva_beam_advance derives the
+// next step's table from this step's parents.
 #include "common.h"
 #include "decode_partial.h"
 #include "rope_append.h"
@@ -127,6 +132,39 @@ __global__ __launch_bounds__(256) void fork_own_partial_kernel(const u32x4* __re
     decode_chunk_partial<kForkKC>(q8, ch, k0, len, qscale, ws_o, ws_ml, mh * nrec + npre_cap + c);
 }
 
+// Beam search's own pass (halva_amd/decode.py:BeamCache): fork_own_partial_kernel with key t of member m fetched from own slot
+// (anc[m][t], h, t) - the ancestry table says whose slot holds row t of m's history; no K / V row is ever copied when a beam continues
+// another beam.  Slots at or beyond own_lens[m] are never read, and neither is any slot (m', t) with m' != anc[m][t] on behalf of m.
+__global__ __launch_bounds__(256) void beam_own_partial_kernel(const u32x4* __restrict__ q, int64_t ldq_chunks, const u32x4* __restrict__ kc,
+                                                               const u32x4* __restrict__ vc, const int32_t* __restrict__ own_lens,
+                                                               const int32_t* __restrict__ anc, int M, int H, int Lown, int npre_cap, int nrec,
+                                                               float qscale, float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+    const int c = blockIdx.x, h = blockIdx.y, m = blockIdx.z;
+    const int len = clampi(own_lens[m], 0, Lown);
+    const int k0 = c * kForkKC;
+    if (k0 >= len) return;
+    const int sub = threadIdx.x & 15;
+    const int64_t mh = (int64_t)m * H + h;
+    const u32x4 q8 = q[(int64_t)m * ldq_chunks + h * kDecChunks + sub];
+    DecChunkRegs<kForkKC> ch;
+    ch.load_via(kc + sub, vc + sub, anc + (int64_t)m * Lown, h, H, Lown, M, k0, len);
+    decode_chunk_partial<kForkKC>(q8, ch, k0, len, qscale, ws_o, ws_ml, mh * nrec + npre_cap + c);
+}
+
+// The ancestry table of the next step from this step's parents, one workgroup per member: with t = own_lens[m] (before this step's
+// append), dst[m][j] = src[parent[m]][j] for j < t and dst[m][t] = m, the slot halva_fork_rope_append is about to write.  dst[m][j] for
+// j > t is not written; a parent outside [0, M) or t outside [0, Lown) leaves row m untouched.
+__global__ __launch_bounds__(256) void beam_advance_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst,
+                                                           const int32_t* __restrict__ parent, const int32_t* __restrict__ own_lens, int M, int Lown) {
+    const int m = blockIdx.x;
+    const int p = parent[m], t = own_lens[m];
+    if (p < 0 || p >= M || t < 0 || t >= Lown) return;
+    const int32_t* s = src + (int64_t)p * Lown;
+    int32_t* d = dst + (int64_t)m * Lown;
+    for (int j = threadIdx.x; j < t; j += blockDim.x) d[j] = s[j];
+    if (threadIdx.x == 0) d[t] = m;
+}
+
 // Combine: one workgroup of 128 threads per (head, member) merges the ceil(prefix_lens[p] / KC) prefix records and then the
 // ceil(own_lens[m] / KC) own records, in that order, in the log2 domain as decode_attn_combine_kernel does.
 __global__ __launch_bounds__(128) void fork_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
@@ -233,6 +271,51 @@ extern "C" int halva_fork_decode_attn(const void* q, int64_t ldq, const void* pk
     hipLaunchKernelGGL(fork_combine_kernel, dim3(H, M), dim3(kDecD), 0, (hipStream_t)stream, ws_o, ws_ml, prefix_lens, prefix_of, own_lens, P, H,
                        Lpre, Lown, npre_cap, nrec, (bf16_t*)out, ld_out);
     HALVA_CHECK_LAUNCH("fork_decode_attn");
+    return HALVA_OK;
+}
+
+extern "C" int halva_beam_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens,
+                                      const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, const int32_t* anc,
+                                      void* out, int64_t ld_out, void* ws, int64_t ws_bytes, int M, int P, int H, int D, int Lpre, int Lown,
+                                      float scale, void* stream) {
+    HALVA_CHECK_ARG(q && pk && pv && prefix_lens && prefix_of && kown && vown && own_lens && anc && out && ws, "beam_decode_attn: null pointer");
+    HALVA_CHECK_ARG(D == kDecD, "beam_decode_attn: head_dim=%d (only 128)", D);
+    HALVA_CHECK_ARG(M > 0 && P > 0 && H > 0 && Lpre > 0 && Lown > 0 && H <= 65535 && M <= 65535,
+                    "beam_decode_attn: bad M=%d / P=%d / H=%d / Lpre=%d / Lown=%d", M, P, H, Lpre, Lown);
+    HALVA_CHECK_ARG(ldq >= (int64_t)H * D && ldq % 8 == 0, "beam_decode_attn: q row stride %lld (needs >= H*D and a multiple of 8)", (long long)ldq);
+    HALVA_CHECK_ARG(ld_out >= (int64_t)H * D, "beam_decode_attn: out row stride %lld < H*D", (long long)ld_out);
+    HALVA_CHECK_ARG(((uintptr_t)q | (uintptr_t)pk | (uintptr_t)pv | (uintptr_t)kown | (uintptr_t)vown | (uintptr_t)ws) % 16 == 0,
+                    "beam_decode_attn: q / cache / workspace pointers must be 16-byte aligned");
+    HALVA_CHECK_ARG((uintptr_t)anc % 4 == 0, "beam_decode_attn: the ancestry table must be 4-byte aligned");
+    const int64_t need = fork_ws_bytes(M, H, Lpre, Lown);
+    HALVA_CHECK_ARG(ws_bytes >= need, "beam_decode_attn: workspace of %lld bytes, %lld needed (halva_fork_decode_attn_ws_bytes)",
+                    (long long)ws_bytes, (long long)need);
+    if (scale <= 0.f) scale = 1.0f / sqrtf((float)D);
+    const int npre_cap = (Lpre + kForkKC - 1) / kForkKC, nown_cap = (Lown + kForkKC - 1) / kForkKC, nrec = npre_cap + nown_cap;
+    float* ws_o = (float*)ws;
+    float* ws_ml = ws_o + (int64_t)M * H * nrec * kDecD;
+    const float qscale = scale * 1.4426950408889634f;
+    hipLaunchKernelGGL(fork_prefix_partial_kernel, dim3(npre_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
+                       (const u32x4*)pk, (const u32x4*)pv, prefix_lens, prefix_of, M, P, H, Lpre, nrec, qscale, ws_o, ws_ml);
+    hipLaunchKernelGGL(beam_own_partial_kernel, dim3(nown_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
+                       (const u32x4*)kown, (const u32x4*)vown, own_lens, anc, M, H, Lown, npre_cap, nrec, qscale, ws_o, ws_ml);
+    hipLaunchKernelGGL(fork_combine_kernel, dim3(H, M), dim3(kDecD), 0, (hipStream_t)stream, ws_o, ws_ml, prefix_lens, prefix_of, own_lens, P, H,
+                       Lpre, Lown, npre_cap, nrec, (bf16_t*)out, ld_out);
+    HALVA_CHECK_LAUNCH("beam_decode_attn");
+    return HALVA_OK;
+}
+
+extern "C" int halva_beam_advance(const int32_t* anc_src, int32_t* anc_dst, const int32_t* parent, const int32_t* own_lens, int M, int Lown,
+                                  void* stream) {
+    HALVA_CHECK_ARG(anc_src && anc_dst && parent && own_lens, "beam_advance: null pointer");
+    HALVA_CHECK_ARG(M > 0 && Lown > 0 && M <= 65535, "beam_advance: bad M=%d / Lown=%d", M, Lown);
+    HALVA_CHECK_ARG(((uintptr_t)anc_src | (uintptr_t)anc_dst | (uintptr_t)parent | (uintptr_t)own_lens) % 4 == 0,
+                    "beam_advance: pointers must be 4-byte aligned");
+    const int64_t bytes = (int64_t)M * Lown * (int64_t)sizeof(int32_t);
+    const intptr_t gap = (intptr_t)((uintptr_t)anc_dst - (uintptr_t)anc_src);
+    HALVA_CHECK_ARG(gap >= bytes || gap <= -bytes, "beam_advance: source and destination tables overlap (they are the two halves of one pair)");
+    hipLaunchKernelGGL(beam_advance_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, anc_src, anc_dst, parent, own_lens, M, Lown);
+    HALVA_CHECK_LAUNCH("beam_advance");
     return HALVA_OK;
 }
 

@@ -11,6 +11,10 @@ row).  Prompts are right-padded: sequence b holds positions [0, seq_len[b]).
 A ForkCache gives M members the rows of a parent cache as a shared prefix, read in place, and own rows behind them (n sampled answers to one
 prompt, many questions about one image): K, V bf16 [M, H, Lown, D], own_lens int32 [layers, M], prefix_lens int32 [P] as recorded at fork time.
 
+A BeamCache is the ForkCache of beam search (B prompts x K beams, member b * K + i): beside the own rows it keeps an ancestry table anc
+int32 [2, M, Lown], one pair for all layers - anc[cur][m][t] is the member whose own slot t holds row t of member m's history - so that a
+beam that continues another beam's history moves no K / V row.
+
 The functions below run on a DecodeStack (the Llama stack, the lm_head weight, whether the LoRA factors apply).  They also accept either
 model wrapper, which hands over its own pieces through decode_stack(): LLaVA's `.model` / `.lm_head`, VILA's `.llm.model` /
 `.llm.lm_head`.
@@ -20,6 +24,7 @@ from collections import namedtuple
 import torch
 
 from . import kernels as K
+from .beam import BeamOutput, BeamState, check_beam_args
 
 DecodeStack = namedtuple("DecodeStack", "lm lm_head use_lora")
 DecodeStack.__doc__ = "lm: halva_amd.llama.LlamaModel; lm_head: the [V, d] head weight; use_lora: apply the LoRA factors (unmerged)."
@@ -419,6 +424,30 @@ class DecodeSession:
         logits = self.logits[torch.tensor(prefix_of, dtype=torch.long, device=self.logits.device)]
         return ForkedSession(self.model, fork, logits, self.config)
 
+    @torch.no_grad()
+    def beam_search(self, num_beams, max_new_tokens, length_penalty=1.0, early_stopping=False, num_return_sequences=1, eos_token_id=None,
+                    pad_token_id=None, stopping_criteria=None, do_sample=False, images=None):
+        """Beam search from the session's rows, with the semantics of HF's generate(num_beams=, do_sample=False) -> BeamOutput(sequences
+        [B * num_return_sequences, L] new tokens only, row b * n_ret + i best first, padded with pad; sequences_scores fp32).  Pending tokens
+        are pushed first, as fork() does; the B * num_beams beams then read this session's rows in place as their prefix, up to the lengths
+        recorded now, and live in a BeamCache this call allocates and drops: the session's lens, pending, logits and cache rows are left as
+        after that push.  Every argument is checked before the first launch."""
+        if images is not None:
+            raise NotImplementedError("session.beam_search: images in a later turn are not implemented; start a new session")
+        dev = self.logits.device
+        eos_ids, pad = eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
+        V = self.logits.shape[-1]
+        Kb, n_ret, C = check_beam_args(num_beams, max_new_tokens, length_penalty, early_stopping, num_return_sequences, eos_ids.numel(), V,
+                                       K.beam_select_limits()[0], do_sample, stopping_criteria)
+        if max(self.lens) + max(len(p) for p in self.pending) > self.max_len:
+            raise RuntimeError("session full: %d rows held, %d pending, max_len=%d" % (max(self.lens), max(len(p) for p in self.pending),
+                                                                                       self.max_len))
+        self._push([[] for _ in self.lens])
+        B = len(self.lens)
+        state = BeamState(B, Kb, max_new_tokens, eos_ids.tolist(), pad, length_penalty, early_stopping, n_ret)
+        beams = BeamCache(self.cache, B, Kb, max(int(max_new_tokens) - 1, 1), self.lens)
+        return beam_loop(self.model, beams, self.logits, state)
+
 
 # ------------------------------------------------------------------------------------------------
 # forks: M members over the rows of a parent cache
@@ -500,6 +529,71 @@ def fork_extend(model, fork, inputs_embeds, n_new):
                         lambda layer, x, i, n_new_d, use_lora, top: layer.fork_extend(x, fork, i, n_new_d, use_lora, top))
 
 
+class BeamCache(ForkCache):
+    """The ForkCache of beam search: B prompts x K beams, member b * K + i reads parent row b.  anc int32 [2, M, Lown] on the device is one
+    double-buffered ancestry table for all layers, `cur` the half in use: anc[cur][m][t], t < own rows, is the member whose own slot t holds
+    row t of member m's history.  All members advance in lockstep (a prompt that is done steps on pad), so every own_lens[l][m] is the same
+    number, `filled` on the host.  K / V rows are never copied or moved."""
+
+    def __init__(self, parent, B, num_beams, Lown, prefix_lens=None):
+        if int(B) != parent.B:
+            raise ValueError("a BeamCache needs one group of beams per parent row (%d), got B=%r" % (parent.B, B))
+        if int(num_beams) < 1:
+            raise ValueError("a BeamCache needs num_beams >= 1, got %r" % (num_beams,))
+        super().__init__(parent, [b for b in range(int(B)) for _ in range(int(num_beams))], Lown, prefix_lens)
+        self.B, self.num_beams = int(B), int(num_beams)
+        self.anc = torch.zeros(2, self.M, self.Lown, dtype=torch.int32, device=self.k[0].device)
+        self.cur = 0
+
+    @property
+    def table(self):
+        return self.anc[self.cur]
+
+
+@torch.no_grad()
+def beam_decode_step(model, beams, token_ids, parents):
+    """One step of every beam: member m pushes token_ids[m] behind the history of member parents[m] (int32 [M] on the device) -> logits
+    [M, V] fp32.  One halva_beam_advance writes the other half of the ancestry table from the current one and the parents, the halves swap,
+    and the layers run: each appends its k / v at own slot own_lens[m] of member m and attends through the table."""
+    if beams.filled >= beams.Lown:
+        raise RuntimeError("KV cache full: %d own slots used of %d; allocate the BeamCache for every pushed token" % (beams.filled, beams.Lown))
+    st = _stack(model)
+    lm = st.lm
+    dev = lm.embed_tokens.weight.device
+    nxt = 1 - beams.cur
+    K.beam_advance(beams.anc[beams.cur], beams.anc[nxt], parents.to(dev, torch.int32), beams.own_lens[0])
+    beams.cur = nxt
+    beams.filled += 1
+    x = lm.embed_tokens(token_ids.to(dev).long())          # a fresh buffer: the residual adds run on it in place
+    x = lm.each_layer(x, None, lambda i, layer, x, top: (layer.beam_decode(x, beams, i, st.use_lora), None))
+    return _lm_head(st, x)
+
+
+@torch.no_grad()
+def beam_loop(model, beams, logits, state, step=None):
+    """The beam loop from (a BeamCache over the prompts' rows, their last-row logits [B, V] fp32, a fresh BeamState) -> BeamOutput.  Per step:
+    one halva_beam_select launch pair on the M rows, ONE host sync that brings its three [B, C] tensors over, BeamState.step on the host,
+    beam_decode_step.  A live prompt whose rows leave nothing to select (NaN or inf logits, or none above -inf) raises RuntimeError on that
+    sync.  step: the function that pushes a column (None = beam_decode_step; tests pass a materialising twin)."""
+    B, Kb, C = state.B, state.K, state.C
+    dev = logits.device
+    logits = logits[torch.arange(B, device=dev).repeat_interleave(Kb)]
+    while True:
+        score, token, beam = K.beam_select(logits, state.run_scores.view(-1).to(dev), Kb, C)
+        host = torch.cat([score.view(torch.int32).view(-1), token.view(-1), beam.view(-1)]).cpu()          # the step's one host sync
+        score, token, beam = host[:B * C].view(torch.float32).view(B, C), host[B * C:2 * B * C].view(B, C), host[2 * B * C:].view(B, C)
+        bad = (token < 0).any(1) & ~state.closed()
+        if bool(bad.any()):
+            raise RuntimeError("beam_search: prompt %d has no token to select at step %d (NaN or inf logits, or none above -inf)"
+                               % (int(bad.nonzero()[0]), state.n))
+        nxt, parents, finished = state.step(score, token, beam)
+        if finished:
+            break
+        logits = (step or beam_decode_step)(model, beams, nxt.to(dev), parents.to(dev, torch.int32))
+    out = state.finalize()
+    return BeamOutput(out.sequences.to(dev), out.sequences_scores.to(dev))
+
+
 @torch.no_grad()
 def sample_fork(model, inputs_embeds, seq_len, n, max_new_tokens, eos_ids, pad, temperature, top_k, top_p, generator=None,
                 stopping_criteria=None, prefix=None, prefill_chunk=None):
@@ -536,3 +630,6 @@ class ForkedSession(DecodeSession):
 
     def fork(self, n=None, prefix_of=None, max_new=256):
         raise NotImplementedError("forks of forks are not implemented; fork the parent session again")
+
+    def beam_search(self, *args, **kwargs):
+        raise NotImplementedError("beam search from a forked session is not implemented; call beam_search on the parent session")

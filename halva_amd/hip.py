@@ -71,6 +71,12 @@ SIGNATURES = {
     "halva_fork_decode_attn": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P],
     "halva_fork_extend_rope_append": [_P, _L, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "halva_fork_extend_attn": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "halva_beam_decode_attn": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P],
+    "halva_beam_advance": [_P, _P, _P, _P, _I, _I, _P],
+    "halva_beam_select": [_P, _L, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "halva_beam_select_max_vocab": [],
+    "halva_beam_select_max_beams": [],
+    "halva_beam_select_max_candidates": [],
     "halva_sample_top_k_top_p": [_P, _L, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P],
     "halva_sample_max_vocab": [],
 }
@@ -118,6 +124,8 @@ def load():
     lib.halva_extend_attn_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
     lib.halva_fork_decode_attn_ws_bytes.restype = c_int64
     lib.halva_fork_decode_attn_ws_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.halva_beam_select_ws_bytes.restype = c_int64
+    lib.halva_beam_select_ws_bytes.argtypes = [c_int, c_int]
     _lib = lib
     return lib
 

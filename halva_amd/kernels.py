@@ -407,6 +407,67 @@ def fork_extend_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_len
     return out
 
 
+# beam search over a forked cache (halva_amd/decode.py:BeamCache): the own pass of the decode attention reads through an ancestry table
+def beam_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, anc, ws, H, D, out_width=None, ldq=None):
+    """fork_decode_attention with own key t of member m read from slot (anc[m][t], h, t): anc int32 [M, Lown] (halva_beam_decode_attn)."""
+    _chk(q, torch.bfloat16, "q"), _chk(pk, torch.bfloat16, "pk"), _chk(pv, torch.bfloat16, "pv")
+    _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown"), _chk(anc, torch.int32, "anc")
+    _chk_fork(prefix_lens, prefix_of, own_lens)
+    M = q.shape[0]
+    if tuple(anc.shape) != (M, kown.shape[2]):
+        raise ValueError("beam_decode_attention: anc must be [M=%d, Lown=%d], got %s" % (M, kown.shape[2], tuple(anc.shape)))
+    width = out_width or H * D
+    out = torch.empty(M, width, dtype=torch.bfloat16, device=q.device)
+    call("halva_beam_decode_attn", ptr(q), ldq or q.shape[-1], ptr(pk), ptr(pv), ptr(prefix_lens), ptr(prefix_of), ptr(kown), ptr(vown),
+         ptr(own_lens), ptr(anc), ptr(out), width, ptr(ws), ws.numel() * ws.element_size(), M, prefix_lens.shape[0], H, D, pk.shape[2],
+         kown.shape[2], 0.0, stream_ptr())
+    return out
+
+
+def beam_advance(anc_src, anc_dst, parent, own_lens):
+    """anc_dst[m][j] = anc_src[parent[m]][j] for j < t = own_lens[m], anc_dst[m][t] = m; anc_* int32 [M, Lown], parent int32 [M], own_lens
+    one layer's int32 [M] before the step's append (halva_beam_advance)."""
+    _chk(anc_src, torch.int32, "anc_src"), _chk(anc_dst, torch.int32, "anc_dst"), _chk(parent, torch.int32, "parent")
+    _chk(own_lens, torch.int32, "own_lens")
+    M, Lown = anc_src.shape
+    if anc_dst.shape != anc_src.shape or parent.shape != (M,) or own_lens.shape != (M,):
+        raise ValueError("beam_advance: anc_src / anc_dst [M, Lown], parent [M], own_lens [M]; got %s %s %s %s"
+                         % (tuple(anc_src.shape), tuple(anc_dst.shape), tuple(parent.shape), tuple(own_lens.shape)))
+    call("halva_beam_advance", ptr(anc_src), ptr(anc_dst), ptr(parent), ptr(own_lens), M, Lown, stream_ptr())
+    return anc_dst
+
+
+def beam_select_limits():
+    """-> (widest row, most beams, most candidates) halva_beam_select takes (library constants)."""
+    lib = hip.load()
+    return int(lib.halva_beam_select_max_vocab()), int(lib.halva_beam_select_max_beams()), int(lib.halva_beam_select_max_candidates())
+
+
+def beam_select(logits, beam_scores, K, C, ws=None):
+    """The C best continuations per prompt of K beams: fp32 logits [B * K, V] (unit column stride, any row stride >= V), beam_scores fp32
+    [B * K] -> (cand_score fp32, cand_token int32, cand_beam int32), each [B, C], by beam_scores[k] + log_softmax(logits[k])[i] descending,
+    ties by the lower k * V + i (include/halva_hip.h:halva_beam_select).  A prompt with a row that cannot be served gets cand_token -1."""
+    _chk(beam_scores, torch.float32, "beam_scores")
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise TypeError("logits must be a float32 device tensor, got %s on %s" % (logits.dtype, logits.device))
+    K, C = int(K), int(C)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1] or K < 1 or logits.shape[0] % K \
+            or beam_scores.shape != (logits.shape[0],):
+        raise ValueError("beam_select: logits [B * K, V] with unit column stride and contiguous beam_scores [B * K]; got %s %s, %s and K=%d"
+                         % (tuple(logits.shape), logits.stride(), tuple(beam_scores.shape), K))
+    M, V = logits.shape
+    B = M // K
+    dev = logits.device
+    score = torch.empty(B, C, dtype=torch.float32, device=dev)
+    token = torch.empty(B, C, dtype=torch.int32, device=dev)
+    beam = torch.empty(B, C, dtype=torch.int32, device=dev)
+    if ws is None:
+        ws = torch.empty(max(int(hip.load().halva_beam_select_ws_bytes(M, max(C, 1))), 16), dtype=torch.uint8, device=dev)
+    call("halva_beam_select", ptr(logits), logits.stride(0), ptr(beam_scores), ptr(score), ptr(token), ptr(beam), ptr(ws),
+         ws.numel() * ws.element_size(), B, K, C, V, stream_ptr())
+    return score, token, beam
+
+
 def sample_max_vocab():
     """The widest row sample_top_k_top_p takes (a library constant)."""
     return int(hip.load().halva_sample_max_vocab())

@@ -459,6 +459,18 @@ class DecoderLayer(nn.Module):
             return K.fork_decode_attention(qkv, pk, pv, fork.prefix_lens, fork.prefix_of, kc, vc, lens, fork.ws, self.H, self.D, self.o.in_width)
         return self._block(x, attend, use_lora, True, None)
 
+    def beam_decode(self, x, beams, layer_idx, use_lora=True):
+        """fork_decode() for the members of a BeamCache (halva_amd/decode.py): the same append into the member's own slot, then the attention
+        with the own rows read through the ancestry table (beams.table: whose slot holds row t of the member's history)."""
+        pk, pv = beams.parent.k[layer_idx], beams.parent.v[layer_idx]
+        kc, vc, lens = beams.k[layer_idx], beams.v[layer_idx], beams.own_lens[layer_idx]
+
+        def attend(qkv):
+            K.fork_rope_append(qkv, beams.cos, beams.sin, beams.prefix_lens, beams.prefix_of, kc, vc, lens, self.H, self.D)
+            return K.beam_decode_attention(qkv, pk, pv, beams.prefix_lens, beams.prefix_of, kc, vc, lens, beams.table, beams.ws, self.H, self.D,
+                                           self.o.in_width)
+        return self._block(x, attend, use_lora, True, None)
+
     def fork_extend(self, x, fork, layer_idx, n_new_d, use_lora=True, rows=None):
         """extend() for the members of a ForkCache: x [M, n, d], rows and return as there."""
         pk, pv = fork.parent.k[layer_idx], fork.parent.v[layer_idx]

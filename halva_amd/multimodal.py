@@ -22,7 +22,7 @@ from . import splice as SP
 
 IGNORE_INDEX = -100
 IMAGE_TOKEN_INDEX = -200
-_LEFT_PADDED = "generate: left-padded prompts are not supported; pad on the right and pass attention_mask"
+_LEFT_PADDED = "%s: left-padded prompts are not supported; pad on the right and pass attention_mask"
 
 
 class CausalLMOutput(SimpleNamespace):
@@ -184,17 +184,17 @@ class MultimodalMixin:
         from .decode import DecodeStack
         return DecodeStack(self.get_model(), self.lm_head.weight, self._use_lora)
 
-    def _embed_prompt(self, input_ids, images, attention_mask):
+    def _embed_prompt(self, input_ids, images, attention_mask, who="generate"):
         """The front part of generation: the prompt spliced when there are images, a tower and more than one token, else embedded.
         Right padding only.  -> (inputs_embeds [B, T, d], seq_len int32 [B] on the host)."""
         if input_ids is None or input_ids.ndim != 2:
-            raise ValueError("generate needs input_ids [B, T]")
+            raise ValueError("%s needs input_ids [B, T]" % who)
         dev = self.device
         ids = input_ids.to(dev)
         mask = None if attention_mask is None else attention_mask.to(dev)
         B, T0 = ids.shape
         if self.left_padding_refused_before_splice and mask is not None and int(SP.spans_from_mask(_cpu(mask))[0].max()) != 0:
-            raise NotImplementedError(_LEFT_PADDED)            # (the splice would re-pad such rows to the right)
+            raise NotImplementedError(_LEFT_PADDED % who)      # (the splice would re-pad such rows to the right)
         embeds = None
         if images is not None:
             images = [im.to(dev, torch.bfloat16) for im in images] if type(images) is list else images.to(dev, torch.bfloat16)
@@ -211,7 +211,7 @@ class MultimodalMixin:
             else:
                 seq_start, seq_len = SP.spans_from_mask(_cpu(mask))
         if int(seq_start.max()) != 0:
-            raise NotImplementedError(_LEFT_PADDED)
+            raise NotImplementedError(_LEFT_PADDED % who)
         return embeds, seq_len
 
     @torch.no_grad()
@@ -245,6 +245,39 @@ class MultimodalMixin:
                              stopping_criteria=stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
         return out if prompt is None else torch.cat([prompt.long(), out], 1)
 
+    def _prompt_session(self, embeds, seq_len, max_len, prefill_chunk):
+        """A cache of max_len slots and the prompt pass over an embedded prompt (_embed_prompt's pair), in blocks of prefill_chunk rows when
+        given -> decode.DecodeSession on that cache with the last-row logits kept."""
+        from . import decode as DEC
+        cache = DEC.KVCache(self, embeds.shape[0], int(max_len), embeds.device)
+        if prefill_chunk is None:
+            logits = DEC.prefill(self, embeds, seq_len, cache)
+        else:
+            logits = DEC.prefill_chunked(self, embeds, seq_len, cache, prefill_chunk)
+        cache.filled = int(seq_len.max())
+        return DEC.DecodeSession(self, cache, logits, seq_len.tolist(), self._lm_config())
+
+    @torch.no_grad()
+    def beam_search(self, input_ids, images=None, attention_mask=None, num_beams=1, max_new_tokens=None, length_penalty=1.0,
+                    early_stopping=False, num_return_sequences=1, eos_token_id=None, pad_token_id=None, stopping_criteria=None, do_sample=False,
+                    prefill_chunk=None):
+        """Beam search with the semantics of HF's generate(num_beams=, do_sample=False) -> decode.BeamOutput(sequences [B * n_ret, L],
+        sequences_scores [B * n_ret]): the new tokens only, on both model families.  _embed_prompt, ONE prompt pass at batch B into a cache of
+        the prompt's rows, then DecodeSession.beam_search on it: the B * num_beams beams read those rows in place and no K / V row moves when
+        a beam continues another beam (decode.BeamCache).  Every argument rule is checked before the first launch.  generate(num_beams > 1)
+        still raises NotImplementedError."""
+        from . import decode as DEC
+        from . import kernels as K
+        from .beam import check_beam_args
+        eos_ids, _ = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, "cpu")
+        check_beam_args(num_beams, max_new_tokens, length_penalty, early_stopping, num_return_sequences, eos_ids.numel(),
+                        self.lm_head.weight.shape[0], K.beam_select_limits()[0], do_sample, stopping_criteria)
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("beam_search: prefill_chunk=%r (needs an int >= 1, or None)" % (prefill_chunk,))
+        embeds, seq_len = self._embed_prompt(input_ids, images, attention_mask, "beam_search")
+        session = self._prompt_session(embeds, seq_len, embeds.shape[1], prefill_chunk)
+        return session.beam_search(num_beams, max_new_tokens, length_penalty, early_stopping, num_return_sequences, eos_token_id, pad_token_id)
+
     @torch.no_grad()
     def start_session(self, input_ids, images=None, attention_mask=None, max_len=None, prefill_chunk=None):
         """A decoding session that keeps its KV cache between calls (halva_amd/decode.py:DecodeSession): the prompt is spliced and embedded
@@ -252,7 +285,6 @@ class MultimodalMixin:
         allocated and prefilled (in blocks of prefill_chunk rows when given), and the last-row logits are kept.  Then
         session.generate(max_new_tokens, ...) -> the new tokens [B, n], session.append(input_ids, attention_mask) for a text-only next
         turn; session.lens is the host list of rows held per sequence."""
-        from . import decode as DEC
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("start_session: prefill_chunk=%r (needs an int >= 1, or None)" % (prefill_chunk,))
         embeds, seq_len = self._embed_prompt(input_ids, images, attention_mask)
@@ -261,10 +293,4 @@ class MultimodalMixin:
             max_len = max(getattr(self._lm_config(), "tokenizer_model_max_length", None) or 0, T + 256)
         if int(max_len) < T:
             raise ValueError("start_session: max_len=%d is below the prompt's %d rows" % (max_len, T))
-        cache = DEC.KVCache(self, embeds.shape[0], int(max_len), embeds.device)
-        if prefill_chunk is None:
-            logits = DEC.prefill(self, embeds, seq_len, cache)
-        else:
-            logits = DEC.prefill_chunked(self, embeds, seq_len, cache, prefill_chunk)
-        cache.filled = int(seq_len.max())
-        return DEC.DecodeSession(self, cache, logits, seq_len.tolist(), self._lm_config())
+        return self._prompt_session(embeds, seq_len, max_len, prefill_chunk)

@@ -380,6 +380,41 @@ int halva_fork_extend_attn(const void* q, int64_t ldrow, int64_t ldseq, const vo
                            const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, const int32_t* n_new, void* out,
                            int64_t ld_out_row, int64_t ld_out_seq, int M, int n, int P, int H, int D, int Lpre, int Lown, float scale, void* stream);
 
+/* ---- Beam search over a forked cache (halva_amd/decode.py:BeamCache, beam_search).  HF re-gathers every layer's cache by the chosen beams
+ * after every step (`reorder_cache`: an index_select over all K / V rows); here the M = B * K members of a fork (prefix_of[m] = m / K) write
+ * own slot (m, t) once and never move it, and an ancestry table anc int32 [M, Lown] says, for member m and own row t < own_lens[m], whose own
+ * slot t holds row t of m's history.
+ *
+ * halva_beam_decode_attn: halva_fork_decode_attn with key t of member m's own pass fetched from slot (anc[m][t], h, t).  The prefix pass, the
+ * combine pass, the workspace and every reduction order are halva_fork_decode_attn's: with anc[m][t] = m the two give the same bits, and with
+ * any table the bits of the fork attention on own caches materialised by that gather.  A table entry outside [0, M) is clamped into it (never
+ * an address outside the caches).  Own slots at or beyond own_lens[m], and slots (m', t) with m' != anc[m][t], are never read for member m. */
+int halva_beam_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens, const int32_t* prefix_of,
+                           const void* kown, const void* vown, const int32_t* own_lens, const int32_t* anc, void* out, int64_t ld_out,
+                           void* ws, int64_t ws_bytes, int M, int P, int H, int D, int Lpre, int Lown, float scale, void* stream);
+/* The next step's table from this step's parents: with t = own_lens[m] (one layer's lengths, BEFORE this step's append),
+ * anc_dst[m][j] = anc_src[parent[m]][j] for j < t and anc_dst[m][t] = m - the slot halva_fork_rope_append is about to write.  anc_dst[m][j]
+ * for j > t is not written.  A parent outside [0, M), or t outside [0, Lown), leaves row m of anc_dst untouched.  The two tables must not
+ * overlap (anc_dst == anc_src included): HALVA_ERR_INVALID_ARG. */
+int halva_beam_advance(const int32_t* anc_src, int32_t* anc_dst, const int32_t* parent, const int32_t* own_lens, int M, int Lown, void* stream);
+/* Candidate selection, one prompt = K consecutive rows: logits fp32 [B * K, V] with row stride ld >= V, beam_scores fp32 [B * K] ->
+ * cand_score fp32, cand_token int32, cand_beam int32, each [B, C]: the C best of the prompt's K * V values
+ *     beam_scores[k] + (x_i - lse_k),   lse_k = max + log(sum exp(x - max))  of row k in fp32,
+ * descending, ties by the lower flat index k * V + i; cand_beam is k (within the prompt), cand_token is i.  What HF's beam search computes as
+ * log_softmax + running score, reshape to [B, K * V], topk(C) - without materialising [B, K * V] and without a sort: a row pass (one
+ * 1024-lane workgroup per row holds it in registers, finds the row's own C-th largest score by count-bisection and compacts its <= C
+ * survivors) and a group pass that ranks the K * C survivors by counting.  Every sum runs in one order fixed by V alone, no float atomics: a
+ * prompt's outputs are bitwise the same for any B, at any position and row stride.  If a row holds a NaN or +inf, or nothing above -inf, or
+ * its beam score is not finite, every cand_token of that prompt is -1 (cand_beam -1, cand_score NaN); other prompts are unaffected.
+ * Limits: V <= halva_beam_select_max_vocab() (32768), K <= halva_beam_select_max_beams() (16), K <= C <= min(64, K * V)
+ * (halva_beam_select_max_candidates()); anything else is HALVA_ERR_INVALID_ARG.  ws_bytes >= halva_beam_select_ws_bytes(B * K, C). */
+int halva_beam_select(const float* logits, int64_t ld, const float* beam_scores, float* cand_score, int32_t* cand_token, int32_t* cand_beam,
+                      void* ws, int64_t ws_bytes, int B, int K, int C, int V, void* stream);
+int halva_beam_select_max_vocab(void);
+int halva_beam_select_max_beams(void);
+int halva_beam_select_max_candidates(void);
+int64_t halva_beam_select_ws_bytes(int M, int C);
+
 /* ---- Sampling (generate with do_sample=True, halva_amd/decode.py:sample).  replaces what HF's generate runs per step behind the reference's
  * `model.generate(..., do_sample=True, temperature=args.temperature, top_p=args.top_p, ...)` (eval_hall/model_chair_loader.py:124-130):
  * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper(min_tokens_to_keep=1) -> softmax -> torch.multinomial, i.e. about ten

@@ -26,7 +26,15 @@ alternately in one process and their outputs compared.  With the model: `sampled
 (decode.sample_fork) beside decode.sample on the prompt repeated 16 times - ms/step, prefill ms, cache GB; `questions`, 16 questions of 32
 ids forked from one 639-row prompt and appended beside a fresh B = 16 start_session on the concatenated prompts.  Measurement only, no gate.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--fork] [--out profiles/r07_decode.json] [--steps 32]
+--beam: the record gains `beam` (7B geometry, H = 32, K = 5 beams, B = 1 and 4 prompts, prefix 639, own rows 32 and 512).  `attention`: us
+of halva_beam_decode_attn beside halva_fork_decode_attn on the same rows with an identity ancestry table, timed alternately, outputs compared
+bitwise.  `reorder`: us per step of halva_beam_advance beside the index_select of all layers' own K / V by the parents that the table
+replaces, and the bytes either moves.  `select`: us of halva_beam_select beside log_softmax + topk over [B, K * V] in torch, V = 32000, and whether the two return the same
+candidates - on the fp32 logits that are timed, on the same logits rounded to bf16 and on their roundings to multiples of 0.5 (ties inside a
+row), with every differing place and its float64 score gap.
+With the model: `loop`, ms/step of the beam loop beside the greedy loop on the same prompts.  Measurement only, no gate.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--fork] [--beam] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
@@ -373,6 +381,138 @@ def fork_question_numbers(m, text=64, image=336, turn=32):
     return {"prompt_rows": ses.lens[0], "questions": n, "turn_ids": turn, "fork_append_ms": round(f_ms, 2), "fresh_prefill_ms": round(fresh_ms, 2)}
 
 
+BEAM_K, BEAM_PREFIX, BEAM_OWN = 5, 639, (32, 512)
+
+
+def _alternately(a, b, reps, rounds):
+    ta, tb = [], []
+    for _ in range(rounds):                       # alternately: other work shares the machine
+        ta.append(_time(a, reps, warmup=5))
+        tb.append(_time(b, reps, warmup=5))
+    return statistics.median(ta), statistics.median(tb), ta, tb
+
+
+def _select_compare(K, logits, scores, B, Kb, C, V):
+    """halva_beam_select beside log_softmax + topk on the same inputs: whether the candidate lists are equal, and for every place where they
+    differ the two flat indices and the float64 gap between their scores (0 = a tie that each side's tie rule ordered its own way)."""
+    s, t, b = K.beam_select(logits, scores, Kb, C)
+    mine = (b.long() * V + t.long()).cpu()
+    theirs = (torch.log_softmax(logits, -1) + scores[:, None]).view(B, Kb * V).topk(C, 1).indices.cpu()
+    x = logits.double().cpu()
+    flat = (scores.double().cpu()[:, None] + (x - torch.logsumexp(x, 1)[:, None])).view(B, Kb * V)
+    diff = []
+    for p, r in (mine != theirs).nonzero().tolist():
+        a, o = int(mine[p, r]), int(theirs[p, r])
+        diff.append({"prompt": p, "rank": r, "native": a, "torch": o, "score_gap_f64": abs(float(flat[p, a] - flat[p, o])),
+                     "logits_equal": bool(logits.view(B, Kb * V)[p, a] == logits.view(B, Kb * V)[p, o]), "same_beam": a // V == o // V})
+    return {"same_candidates": not diff, "same_candidate_sets": all(sorted(mine[p].tolist()) == sorted(theirs[p].tolist()) for p in range(B)),
+            "differing": diff[:16]}
+
+
+def beam_kernel_numbers(H=32, D=128, layers=32, V=32000, reps=50, rounds=3):
+    from halva_amd import kernels as K
+    dev = "cuda"
+    Kb, prefix = BEAM_K, BEAM_PREFIX
+    att, reorder, select = {}, {}, {}
+    for B in (1, 4):
+        M = B * Kb
+        pk = torch.randn(B, H, prefix, D, device=dev).to(torch.bfloat16)
+        pv = torch.randn(B, H, prefix, D, device=dev).to(torch.bfloat16)
+        plens = torch.full((B,), prefix, dtype=torch.int32, device=dev)
+        of = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Kb)
+        q = torch.randn(M, 3 * H * D, device=dev).to(torch.bfloat16)
+        parents = (torch.arange(B, device=dev).repeat_interleave(Kb) * Kb + torch.randint(0, Kb, (M,), device=dev)).to(torch.int32)
+        for own in BEAM_OWN:
+            Lown = own + 1
+            kc = torch.randn(M, H, Lown, D, device=dev).to(torch.bfloat16)
+            vc = torch.randn(M, H, Lown, D, device=dev).to(torch.bfloat16)
+            olens = torch.full((M,), own, dtype=torch.int32, device=dev)
+            ws = torch.empty(K.fork_ws_bytes(M, H, prefix, Lown), dtype=torch.uint8, device=dev)
+            anc = torch.arange(M, dtype=torch.int32, device=dev)[:, None].expand(M, Lown).contiguous()
+            beam = lambda: K.beam_decode_attention(q, pk, pv, plens, of, kc, vc, olens, anc, ws, H, D)      # noqa: E731
+            fork = lambda: K.fork_decode_attention(q, pk, pv, plens, of, kc, vc, olens, ws, H, D)           # noqa: E731
+            same = bool(torch.equal(beam().view(torch.int16), fork().view(torch.int16)))
+            b_ms, f_ms, tb, tf = _alternately(beam, fork, reps, rounds)
+            att["B%d_own%d" % (B, own)] = {"members": M, "prefix": prefix, "own": own, "bitwise_equal": same,
+                                           "beam_us": round(b_ms * 1e3, 2), "fork_us": round(f_ms * 1e3, 2),
+                                           "beam_us_rounds": [round(t * 1e3, 2) for t in tb], "fork_us_rounds": [round(t * 1e3, 2) for t in tf]}
+            # what the table replaces: every layer's own K and V gathered by the parents, each step
+            ks = [torch.randn(M, H, Lown, D, device=dev).to(torch.bfloat16) for _ in range(2 * layers)]
+            idx = parents.long()
+            anc2 = torch.zeros(2, M, Lown, dtype=torch.int32, device=dev)
+            anc2[0] = anc
+            hold = {}
+
+            def gather():
+                hold["out"] = [t.index_select(0, idx) for t in ks]
+
+            def advance():
+                K.beam_advance(anc2[0], anc2[1], parents, olens)
+            g_ms, a_ms, tg, ta = _alternately(gather, advance, max(reps // 5, 5), rounds)
+            reorder["B%d_own%d" % (B, own)] = {"layers": layers, "index_select_us_per_step": round(g_ms * 1e3, 1),
+                                               "index_select_bytes": 2 * 2 * layers * M * H * own * D * 2,
+                                               "beam_advance_us_per_step": round(a_ms * 1e3, 2), "beam_advance_bytes": 2 * 4 * M * own}
+            del ks, hold
+        scores = -torch.rand(M, device=dev) * 4
+        C = 2 * Kb
+        raw = 8.0 * torch.randn(M, V, device=dev)
+        # timed on fp32 logits; compared on those, on the same logits rounded to bf16 and on their roundings to multiples of 0.5, where equal
+        # values inside a row leave the order to each side's tie rule (the kernel's: lower flat index; torch.topk's: unspecified)
+        rec = {"K": Kb, "C": C, "V": V}
+        for name, logits in (("fp32_logits", raw), ("bf16_rounded_logits", raw.bfloat16().float()),
+                             ("half_integer_logits", torch.round(raw * 2) / 2)):
+            rec[name] = _select_compare(K, logits, scores, B, Kb, C, V)
+        logits = raw
+        native = lambda: K.beam_select(logits, scores, Kb, C)                                                # noqa: E731
+        composed = lambda: (torch.log_softmax(logits, -1) + scores[:, None]).view(B, Kb * V).topk(C, 1)     # noqa: E731
+        n_ms, c_ms, _, _ = _alternately(native, composed, reps, rounds)
+        rec.update({"native_us": round(n_ms * 1e3, 2), "torch_us": round(c_ms * 1e3, 2)})
+        select["B%d" % B] = rec
+    return {"attention": att, "reorder": reorder, "select": select}
+
+
+def beam_loop_numbers(m, steps, text=64, image=336):
+    """ms per step of the whole beam loop (select, host sync, BeamState, advance, layers) beside the greedy loop on the same prompts:
+    (a run of steps + 1 tokens - a run of 1 token) / steps; no EOS id, so every run takes all its steps."""
+    import time
+    from halva_amd import decode as DEC
+    g = torch.Generator().manual_seed(0)
+    none = torch.empty(0, dtype=torch.long, device="cuda")
+    res = {}
+    for B in (1, 4):
+        ids = torch.randint(3, 32000, (B, text), generator=g)
+        ids[:, 0] = 1
+        ids[:, 6] = -200
+        images = torch.randn(B, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+        with torch.no_grad():
+            embeds, plan = m._splice(ids.cuda(), None, None, None, images)
+
+        def wall(fn, n):
+            best = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(n)
+                torch.cuda.synchronize()
+                best.append(time.perf_counter() - t0)
+            return statistics.median(best) * 1e3
+
+        def greedy(n):
+            DEC.greedy(m, embeds, plan.seq_len, n, none, 0)
+
+        def beams(n):
+            cache = DEC.KVCache(m, B, embeds.shape[1])
+            logits = DEC.prefill(m, embeds, plan.seq_len, cache)
+            cache.filled = int(plan.seq_len.max())
+            ses = DEC.DecodeSession(m, cache, logits, plan.seq_len.tolist(), m._lm_config())
+            ses.beam_search(BEAM_K, n, eos_token_id=[], early_stopping="never")
+        greedy(2), beams(2)
+        res["B%d" % B] = {"prompt_rows": embeds.shape[1], "beams": BEAM_K, "steps": steps,
+                          "greedy_ms_per_step": round((wall(greedy, steps + 1) - wall(greedy, 1)) / steps, 3),
+                          "beam_ms_per_step": round((wall(beams, steps + 1) - wall(beams, 1)) / steps, 3)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -385,6 +525,9 @@ def main():
     ap.add_argument("--fork", action="store_true",
                     help="also time the fork decode attention beside 16 materialised caches, the num_return_sequences=16 loop beside the "
                          "repeated prompt, and 16 forked questions beside a fresh prefill")
+    ap.add_argument("--beam", action="store_true",
+                    help="also time the beam decode attention beside the fork attention (identity table), halva_beam_advance beside the "
+                         "index_select it replaces, halva_beam_select beside log_softmax + topk, and the beam loop beside the greedy loop")
     a = ap.parse_args()
     from halva_amd import hip
     hip.load()
@@ -398,6 +541,8 @@ def main():
         rec["extend"] = extend_kernel_numbers()
     if a.fork:
         rec["fork"] = {"attention": fork_kernel_numbers(H=40 if vila else 32)}
+    if a.beam:
+        rec["beam"] = beam_kernel_numbers(H=40 if vila else 32, layers=40 if vila else 32)
     if not a.skip_model:
         m = model_vila13b() if vila else model_7b()
         def weights_gb():
@@ -414,6 +559,8 @@ def main():
         if a.fork:
             rec["fork"]["sampled_loop"] = fork_loop_numbers(m, a.steps, text=60, image=384) if vila else fork_loop_numbers(m, a.steps)
             rec["fork"]["questions"] = fork_question_numbers(m, text=60, image=384) if vila else fork_question_numbers(m)
+        if a.beam:
+            rec["beam"]["loop"] = beam_loop_numbers(m, a.steps, text=60, image=384) if vila else beam_loop_numbers(m, a.steps)
         if a.merged:
             import time
             torch.cuda.synchronize()
