@@ -16,9 +16,9 @@
 // Pushing n rows per member: extend.hip's two kernels with the prefix in front (extend_attn.h's body with its prefix phase on).
 //
 // Beam search (halva_amd/decode.py:BeamCache): the members are B prompts x K beams, and a beam that continues another beam's history moves
-// no K / V row - an ancestry table anc int32 [M, Lown] names, per member and own row, the member whose slot holds it.  halva_beam_decode_attn
-// is the decode step's three launches with the own pass reading through the table (beam_own_partial_kernel); halva_beam_advance derives the
-// next step's table from this step's parents.
+// no K / V row - an ancestry table anc int32 [M, Lown] names, per member and own row, the member whose slot holds it.  halva_fork_decode_attn
+// and halva_beam_decode_attn are one launcher (fork_decode_attn: the checks and the three launches); given a table, its own pass reads
+// through it (beam_own_partial_kernel).  halva_beam_advance derives the next step's table from this step's parents.
 #include "common.h"
 #include "decode_partial.h"
 #include "rope_append.h"
@@ -244,21 +244,22 @@ extern "C" int halva_fork_rope_append(void* qkv, int64_t ldqkv, const void* cos,
     return HALVA_OK;
 }
 
-extern "C" int halva_fork_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens,
-                                      const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, void* out,
-                                      int64_t ld_out, void* ws, int64_t ws_bytes, int M, int P, int H, int D, int Lpre, int Lown, float scale,
-                                      void* stream) {
-    HALVA_CHECK_ARG(q && pk && pv && prefix_lens && prefix_of && kown && vown && own_lens && out && ws, "fork_decode_attn: null pointer");
-    HALVA_CHECK_ARG(D == kDecD, "fork_decode_attn: head_dim=%d (only 128)", D);
-    HALVA_CHECK_ARG(M > 0 && P > 0 && H > 0 && Lpre > 0 && Lown > 0 && H <= 65535 && M <= 65535,
-                    "fork_decode_attn: bad M=%d / P=%d / H=%d / Lpre=%d / Lown=%d", M, P, H, Lpre, Lown);
-    HALVA_CHECK_ARG(ldq >= (int64_t)H * D && ldq % 8 == 0, "fork_decode_attn: q row stride %lld (needs >= H*D and a multiple of 8)", (long long)ldq);
-    HALVA_CHECK_ARG(ld_out >= (int64_t)H * D, "fork_decode_attn: out row stride %lld < H*D", (long long)ld_out);
+// The decode attention of forks and beams: every check, then the prefix pass, the own pass - through the ancestry table anc when one is
+// given, plain when anc is null - and the combine.  name: the entry's, for its error messages.
+static int fork_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens, const int32_t* prefix_of,
+                            const void* kown, const void* vown, const int32_t* own_lens, void* out, int64_t ld_out, void* ws, int64_t ws_bytes,
+                            int M, int P, int H, int D, int Lpre, int Lown, float scale, void* stream, const int32_t* anc, const char* name) {
+    HALVA_CHECK_ARG(q && pk && pv && prefix_lens && prefix_of && kown && vown && own_lens && out && ws, "%s: null pointer", name);
+    HALVA_CHECK_ARG(D == kDecD, "%s: head_dim=%d (only 128)", name, D);
+    HALVA_CHECK_ARG(M > 0 && P > 0 && H > 0 && Lpre > 0 && Lown > 0 && H <= 65535 && M <= 65535, "%s: bad M=%d / P=%d / H=%d / Lpre=%d / Lown=%d",
+                    name, M, P, H, Lpre, Lown);
+    HALVA_CHECK_ARG(ldq >= (int64_t)H * D && ldq % 8 == 0, "%s: q row stride %lld (needs >= H*D and a multiple of 8)", name, (long long)ldq);
+    HALVA_CHECK_ARG(ld_out >= (int64_t)H * D, "%s: out row stride %lld < H*D", name, (long long)ld_out);
     HALVA_CHECK_ARG(((uintptr_t)q | (uintptr_t)pk | (uintptr_t)pv | (uintptr_t)kown | (uintptr_t)vown | (uintptr_t)ws) % 16 == 0,
-                    "fork_decode_attn: q / cache / workspace pointers must be 16-byte aligned");
+                    "%s: q / cache / workspace pointers must be 16-byte aligned", name);
     const int64_t need = fork_ws_bytes(M, H, Lpre, Lown);
-    HALVA_CHECK_ARG(ws_bytes >= need, "fork_decode_attn: workspace of %lld bytes, %lld needed (halva_fork_decode_attn_ws_bytes)",
-                    (long long)ws_bytes, (long long)need);
+    HALVA_CHECK_ARG(ws_bytes >= need, "%s: workspace of %lld bytes, %lld needed (halva_fork_decode_attn_ws_bytes)", name, (long long)ws_bytes,
+                    (long long)need);
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)D);
     const int npre_cap = (Lpre + kForkKC - 1) / kForkKC, nown_cap = (Lown + kForkKC - 1) / kForkKC, nrec = npre_cap + nown_cap;
     float* ws_o = (float*)ws;
@@ -266,43 +267,34 @@ extern "C" int halva_fork_decode_attn(const void* q, int64_t ldq, const void* pk
     const float qscale = scale * 1.4426950408889634f;
     hipLaunchKernelGGL(fork_prefix_partial_kernel, dim3(npre_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
                        (const u32x4*)pk, (const u32x4*)pv, prefix_lens, prefix_of, M, P, H, Lpre, nrec, qscale, ws_o, ws_ml);
-    hipLaunchKernelGGL(fork_own_partial_kernel, dim3(nown_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
-                       (const u32x4*)kown, (const u32x4*)vown, own_lens, H, Lown, npre_cap, nrec, qscale, ws_o, ws_ml);
+    if (anc)
+        hipLaunchKernelGGL(beam_own_partial_kernel, dim3(nown_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
+                           (const u32x4*)kown, (const u32x4*)vown, own_lens, anc, M, H, Lown, npre_cap, nrec, qscale, ws_o, ws_ml);
+    else
+        hipLaunchKernelGGL(fork_own_partial_kernel, dim3(nown_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
+                           (const u32x4*)kown, (const u32x4*)vown, own_lens, H, Lown, npre_cap, nrec, qscale, ws_o, ws_ml);
     hipLaunchKernelGGL(fork_combine_kernel, dim3(H, M), dim3(kDecD), 0, (hipStream_t)stream, ws_o, ws_ml, prefix_lens, prefix_of, own_lens, P, H,
                        Lpre, Lown, npre_cap, nrec, (bf16_t*)out, ld_out);
-    HALVA_CHECK_LAUNCH("fork_decode_attn");
+    HALVA_CHECK_LAUNCH(name);
     return HALVA_OK;
+}
+
+extern "C" int halva_fork_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens,
+                                      const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, void* out,
+                                      int64_t ld_out, void* ws, int64_t ws_bytes, int M, int P, int H, int D, int Lpre, int Lown, float scale,
+                                      void* stream) {
+    return fork_decode_attn(q, ldq, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, out, ld_out, ws, ws_bytes, M, P, H, D, Lpre, Lown, scale,
+                            stream, nullptr, "fork_decode_attn");
 }
 
 extern "C" int halva_beam_decode_attn(const void* q, int64_t ldq, const void* pk, const void* pv, const int32_t* prefix_lens,
                                       const int32_t* prefix_of, const void* kown, const void* vown, const int32_t* own_lens, const int32_t* anc,
                                       void* out, int64_t ld_out, void* ws, int64_t ws_bytes, int M, int P, int H, int D, int Lpre, int Lown,
                                       float scale, void* stream) {
-    HALVA_CHECK_ARG(q && pk && pv && prefix_lens && prefix_of && kown && vown && own_lens && anc && out && ws, "beam_decode_attn: null pointer");
-    HALVA_CHECK_ARG(D == kDecD, "beam_decode_attn: head_dim=%d (only 128)", D);
-    HALVA_CHECK_ARG(M > 0 && P > 0 && H > 0 && Lpre > 0 && Lown > 0 && H <= 65535 && M <= 65535,
-                    "beam_decode_attn: bad M=%d / P=%d / H=%d / Lpre=%d / Lown=%d", M, P, H, Lpre, Lown);
-    HALVA_CHECK_ARG(ldq >= (int64_t)H * D && ldq % 8 == 0, "beam_decode_attn: q row stride %lld (needs >= H*D and a multiple of 8)", (long long)ldq);
-    HALVA_CHECK_ARG(ld_out >= (int64_t)H * D, "beam_decode_attn: out row stride %lld < H*D", (long long)ld_out);
-    HALVA_CHECK_ARG(((uintptr_t)q | (uintptr_t)pk | (uintptr_t)pv | (uintptr_t)kown | (uintptr_t)vown | (uintptr_t)ws) % 16 == 0,
-                    "beam_decode_attn: q / cache / workspace pointers must be 16-byte aligned");
+    HALVA_CHECK_ARG(anc, "beam_decode_attn: null pointer");
     HALVA_CHECK_ARG((uintptr_t)anc % 4 == 0, "beam_decode_attn: the ancestry table must be 4-byte aligned");
-    const int64_t need = fork_ws_bytes(M, H, Lpre, Lown);
-    HALVA_CHECK_ARG(ws_bytes >= need, "beam_decode_attn: workspace of %lld bytes, %lld needed (halva_fork_decode_attn_ws_bytes)",
-                    (long long)ws_bytes, (long long)need);
-    if (scale <= 0.f) scale = 1.0f / sqrtf((float)D);
-    const int npre_cap = (Lpre + kForkKC - 1) / kForkKC, nown_cap = (Lown + kForkKC - 1) / kForkKC, nrec = npre_cap + nown_cap;
-    float* ws_o = (float*)ws;
-    float* ws_ml = ws_o + (int64_t)M * H * nrec * kDecD;
-    const float qscale = scale * 1.4426950408889634f;
-    hipLaunchKernelGGL(fork_prefix_partial_kernel, dim3(npre_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
-                       (const u32x4*)pk, (const u32x4*)pv, prefix_lens, prefix_of, M, P, H, Lpre, nrec, qscale, ws_o, ws_ml);
-    hipLaunchKernelGGL(beam_own_partial_kernel, dim3(nown_cap, H, M), dim3(64 * kDecWaves), 0, (hipStream_t)stream, (const u32x4*)q, ldq / 8,
-                       (const u32x4*)kown, (const u32x4*)vown, own_lens, anc, M, H, Lown, npre_cap, nrec, qscale, ws_o, ws_ml);
-    hipLaunchKernelGGL(fork_combine_kernel, dim3(H, M), dim3(kDecD), 0, (hipStream_t)stream, ws_o, ws_ml, prefix_lens, prefix_of, own_lens, P, H,
-                       Lpre, Lown, npre_cap, nrec, (bf16_t*)out, ld_out);
-    HALVA_CHECK_LAUNCH("beam_decode_attn");
-    return HALVA_OK;
+    return fork_decode_attn(q, ldq, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, out, ld_out, ws, ws_bytes, M, P, H, D, Lpre, Lown, scale,
+                            stream, anc, "beam_decode_attn");
 }
 
 extern "C" int halva_beam_advance(const int32_t* anc_src, int32_t* anc_dst, const int32_t* parent, const int32_t* own_lens, int M, int Lown,

@@ -15,6 +15,12 @@ A BeamCache is the ForkCache of beam search (B prompts x K beams, member b * K +
 int32 [2, M, Lown], one pair for all layers - anc[cur][m][t] is the member whose own slot t holds row t of member m's history - so that a
 beam that continues another beam's history moves no K / V row.
 
+The three caches share one surface, and nothing above them asks which one it holds: rows (sequences or members), room (rows a member can
+hold), Lcap, lens, filled, full_step (decode_step's message on a full cache), rows_refusal (why extend() is refused, or None),
+attend_step(layer, qkv, H, D, out_width) - RoPE + append of one new row per member, then the single-query attention - and
+attend_rows(layer, qkv, n_new_d, H, D, out_width) - append, attention and advance of up to n rows per member.  decode_step() and extend() are
+written once over it; DecoderLayer.decode / .extend hand the projection to it.
+
 The functions below run on a DecodeStack (the Llama stack, the lm_head weight, whether the LoRA factors apply).  They also accept either
 model wrapper, which hands over its own pieces through decode_stack(): LLaVA's `.model` / `.lm_head`, VILA's `.llm.model` /
 `.llm.lm_head`.
@@ -59,6 +65,23 @@ class KVCache:
             cos, sin = lm.rope(Lcap, dev)
         self.cos, self.sin = cos, sin
 
+    full_step = "KV cache full: %d slots used of %d; allocate the cache for the prompt plus every new token"
+    rows_refusal = None
+    rows = property(lambda self: self.B)
+    room = property(lambda self: min(self.Lcap, self.cos.shape[0]))
+
+    def attend_step(self, layer_idx, qkv, H, D, out_width):
+        kc, vc, lens = self.k[layer_idx], self.v[layer_idx], self.lens[layer_idx]
+        K.decode_rope_append(qkv, self.cos, self.sin, kc, vc, lens, H, D)
+        return K.decode_attention(qkv, kc, vc, lens, self.ws, H, D, out_width)
+
+    def attend_rows(self, layer_idx, qkv, n_new_d, H, D, out_width):
+        kc, vc, lens = self.k[layer_idx], self.v[layer_idx], self.lens[layer_idx]
+        K.extend_rope_append(qkv, self.cos, self.sin, kc, vc, lens, n_new_d, H, D)
+        a = K.extend_attention(qkv, kc, vc, lens, n_new_d, None, H, D, out_width)      # (its workspace is empty by design)
+        K.extend_advance(lens, n_new_d, self.Lcap)
+        return a
+
     def fill(self, layer_idx, qkv, seq_len):
         """Prompt pass: the rotated k and the plain v of the [B, T, 3*H*D] projection into slots [0, T) (rows past seq_len[b] are
         written too and never read), lens = seq_len."""
@@ -93,13 +116,18 @@ def prefill(model, inputs_embeds, seq_len, cache):
     return _lm_head(st, h)
 
 
+def _check_room(cache):
+    if cache.filled >= cache.room:
+        # the append kernels leave a full cache untouched (they never write out of bounds): refuse here instead of attending without the
+        # new token
+        raise RuntimeError(cache.full_step % (cache.filled, cache.Lcap))
+
+
 @torch.no_grad()
 def decode_step(model, cache, token_ids):
-    """One new token per sequence: token_ids [B] -> logits [B, V] fp32.  Appends each layer's k / v at slot lens[b]."""
-    if cache.filled >= min(cache.Lcap, cache.cos.shape[0]):
-        # the append kernel leaves a full cache untouched (it never writes out of bounds): refuse here instead of attending without
-        # the new token
-        raise RuntimeError("KV cache full: %d slots used of %d; allocate the cache for the prompt plus every new token" % (cache.filled, cache.Lcap))
+    """One new token per sequence of a KVCache, or per member of a ForkCache / BeamCache: token_ids [rows] -> logits [rows, V] fp32.  Each
+    layer appends its k / v behind the rows the member holds (cache.attend_step)."""
+    _check_room(cache)
     cache.filled += 1
     st = _stack(model)
     lm = st.lm
@@ -110,37 +138,33 @@ def decode_step(model, cache, token_ids):
 
 @torch.no_grad()
 def extend(model, cache, inputs_embeds, n_new):
-    """Several new rows per sequence in one pass over a cache that already holds rows: inputs_embeds [B, n, d], n_new [B] host ints with
-    0 <= n_new[b] <= n (sequence b pushes its rows [0, n_new[b]) at positions lens[b] ..) -> logits [B, V] fp32 of each sequence's last new
-    row.  A sequence with n_new[b] == 0 is left as it is (cache and lens untouched) and gets NaN logits: callers mask them.  Every check
-    runs before the first launch; a block that does not fit raises RuntimeError like decode_step's."""
-    return _extend_rows(model, cache, inputs_embeds, n_new, "extend", cache.B, min(cache.Lcap, cache.cos.shape[0]), cache.Lcap,
-                        lambda layer, x, i, n_new_d, use_lora, top: layer.extend(x, cache, i, n_new_d, use_lora, top))
-
-
-def _extend_rows(model, cache, inputs_embeds, n_new, name, B, room, slots, run):
-    """The body of extend() and fork_extend(): the host checks, then run(layer, x, layer index, n_new on the device, use_lora, top rows) per
-    layer.  room: the rows the cache can hold; slots: the figure the error message names."""
+    """Several new rows per sequence (or member of a ForkCache) in one pass over a cache that already holds rows: inputs_embeds [B, n, d],
+    n_new [B] host ints with 0 <= n_new[b] <= n (sequence b pushes its rows [0, n_new[b]) behind the rows it holds) -> logits [B, V] fp32
+    of each sequence's last new row.  A sequence with n_new[b] == 0 is left as it is (cache and lens untouched) and gets NaN logits:
+    callers mask them.  Every check runs before the first launch; a block that does not fit raises RuntimeError like decode_step's."""
+    if cache.rows_refusal:
+        raise NotImplementedError(cache.rows_refusal)
     st = _stack(model)
     lm = st.lm
+    B = cache.rows
     if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != B:
-        raise ValueError("%s needs inputs_embeds [B=%d, n, d], got %s" % (name, B, tuple(inputs_embeds.shape)))
-    B, n, _ = inputs_embeds.shape
+        raise ValueError("extend needs inputs_embeds [B=%d, n, d], got %s" % (B, tuple(inputs_embeds.shape)))
+    n = inputs_embeds.shape[1]
     n_new = torch.as_tensor(n_new, dtype=torch.int32).view(-1).cpu()
     if n_new.numel() != B:
-        raise ValueError("%s needs one n_new per sequence (%d), got %d" % (name, B, n_new.numel()))
+        raise ValueError("extend needs one n_new per sequence (%d), got %d" % (B, n_new.numel()))
     most = int(n_new.max())
     if most < 1 or int(n_new.min()) < 0 or most > n:
-        raise ValueError("%s: every n_new[b] must lie in [0, n=%d] and one of them must be >= 1, got %s" % (name, n, n_new.tolist()))
-    if cache.filled + most > room:
+        raise ValueError("extend: every n_new[b] must lie in [0, n=%d] and one of them must be >= 1, got %s" % (n, n_new.tolist()))
+    if cache.filled + most > cache.room:
         raise RuntimeError("KV cache full: %d slots used of %d, %d more asked for; allocate the cache for the prompt plus every new row"
-                           % (cache.filled, slots, most))
+                           % (cache.filled, cache.Lcap, most))
     cache.filled += most
     dev = lm.embed_tokens.weight.device
     n_new_d = n_new.to(dev)
     rows = (torch.arange(B, dtype=torch.int64) * n + (n_new.long() - 1).clamp_(min=0)).to(dev)
     x = inputs_embeds.to(dev, torch.bfloat16, copy=True).contiguous()      # a buffer of our own: the residual adds run on it in place
-    x = lm.each_layer(x, rows, lambda i, layer, x, top: (run(layer, x, i, n_new_d, st.use_lora, top), None))
+    x = lm.each_layer(x, rows, lambda i, layer, x, top: (layer.extend(x, cache, i, n_new_d, st.use_lora, top), None))
     return _lm_head(st, x).masked_fill_((n_new_d == 0)[:, None], float("nan"))
 
 
@@ -182,6 +206,13 @@ def prefill_chunked(model, inputs_embeds, seq_len, cache, chunk):
     return logits
 
 
+def prompt_pass(model, inputs_embeds, seq_len, cache, prefill_chunk=None):
+    """prefill(), or prefill_chunked() in blocks of prefill_chunk rows when one is given."""
+    if prefill_chunk is None:
+        return prefill(model, inputs_embeds, seq_len, cache)
+    return prefill_chunked(model, inputs_embeds, seq_len, cache, prefill_chunk)
+
+
 # ------------------------------------------------------------------------------------------------
 # the generation loop shared by both generate() methods: greedy, or temperature / top-k / top-p sampling
 def check_generate_args(num_beams, do_sample, max_new_tokens, temperature=None, top_k=None, top_p=None):
@@ -220,21 +251,17 @@ def eos_and_pad(config, eos_token_id, pad_token_id, device):
 def _generate_loop(model, inputs_embeds, seq_len, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, prefill_chunk=None):
     """Prefill, then select -> decode_step until every row is done or after max_new_tokens steps -> LongTensor [B, n] of new tokens.
     select(logits [B, V] fp32) -> (next tokens [B], None) or (next tokens [B], bool [B] of rows it could not serve); with the latter the
-    flags ride on the step's one host sync and a set flag of a live row raises.  prefill_chunk: None = one prompt pass, an int = the
-    prompt pass in blocks of that many rows (prefill_chunked)."""
+    flags ride on the step's one host sync and a set flag of a live row raises.  prefill_chunk: as prompt_pass()."""
     B = inputs_embeds.shape[0]
     cache = KVCache(model, B, inputs_embeds.shape[1] + max_new_tokens, inputs_embeds.device)
-    if prefill_chunk is None:
-        logits = prefill(model, inputs_embeds, seq_len, cache)
-    else:
-        logits = prefill_chunked(model, inputs_embeds, seq_len, cache, prefill_chunk)
+    logits = prompt_pass(model, inputs_embeds, seq_len, cache, prefill_chunk)
     return _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)[0]
 
 
-def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, push=None):
+def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix):
     """_generate_loop's steps from a given (cache, logits [B, V]) -> (new tokens [B, n], real [B] on the device: how many of a row's n
-    tokens it selected while live, the others being pad).  The last selected token is not pushed through the model.  push: the function
-    that pushes a column (None = decode_step; fork_decode_step for a ForkCache)."""
+    tokens it selected while live, the others being pad).  The last selected token is not pushed through the model.  cache: any of the
+    three (a ForkCache's rows are its members)."""
     dev = logits.device
     B = logits.shape[0]
     crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
@@ -268,7 +295,7 @@ def _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, stopp
                                    % (flags[1:].index(True), step))
             if step + 1 == max_new_tokens or flags[0]:
                 break
-        logits = (push or decode_step)(model, cache, nxt)
+        logits = decode_step(model, cache, nxt)
     return torch.stack(out, 1), real
 
 
@@ -328,11 +355,6 @@ class DecodeSession:
         self.pending = [[] for _ in self.lens]
         self.max_len = cache.Lcap
 
-    _step = None          # _loop_from's push: None = decode_step
-
-    def _extend(self, embeds, n_new):
-        return extend(self.model, self.cache, embeds, n_new)
-
     def _set_lens(self):
         cache = self.cache
         cache.lens.copy_(torch.tensor(self.lens, dtype=torch.int32).to(cache.lens.device).expand_as(cache.lens))
@@ -352,7 +374,7 @@ class DecodeSession:
         ids = torch.zeros(len(rows), n, dtype=torch.long)
         for b, r in enumerate(rows):
             ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.long)
-        lg = self._extend(lm.embed_tokens(ids.to(dev)), n_new)
+        lg = extend(self.model, self.cache, lm.embed_tokens(ids.to(dev)), n_new)
         live = torch.tensor([v > 0 for v in n_new], device=lg.device)
         self.logits = torch.where(live[:, None], lg, self.logits)
         self.lens = [a + b for a, b in zip(self.lens, n_new)]
@@ -393,7 +415,7 @@ class DecodeSession:
         B = len(self.lens)
         eos_ids, pad = eos_and_pad(self.config, eos_token_id, pad_token_id, dev)
         select = _argmax if sampling is None else _sampler(self.model, B, dev, *sampling, generator)
-        out, real = _loop_from(self.model, self.cache, self.logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, None, self._step)
+        out, real = _loop_from(self.model, self.cache, self.logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, None)
         toks, real = out.tolist(), real.tolist()
         pushed = out.shape[1] - 1                       # every column but the last went through decode_step
         for b in range(B):
@@ -415,7 +437,7 @@ class DecodeSession:
         if n is not None:
             if int(n) < 1:
                 raise ValueError("session.fork: n=%r (needs an int >= 1)" % (n,))
-            prefix_of = [b for b in range(len(self.lens)) for _ in range(int(n))]
+            prefix_of = n_ways(len(self.lens), n)
         prefix_of = check_prefix_of(prefix_of, len(self.lens))
         if max_new is None or int(max_new) < 1:
             raise ValueError("session.fork: max_new=%r (needs an int >= 1)" % (max_new,))
@@ -451,6 +473,11 @@ class DecodeSession:
 
 # ------------------------------------------------------------------------------------------------
 # forks: M members over the rows of a parent cache
+def n_ways(B, n):
+    """prefix_of of B rows forked n ways each: member b * n + i continues row b."""
+    return [b for b in range(int(B)) for _ in range(int(n))]
+
+
 def check_prefix_of(prefix_of, P):
     """-> prefix_of as a list of ints: one parent row index in [0, P) per member, non-decreasing (members of one row are contiguous)."""
     try:
@@ -503,30 +530,31 @@ class ForkCache:
             raise RuntimeError("RoPE tables of %d rows do not cover the fork's %d positions" % (cos.shape[0], need))
         self.cos, self.sin = cos, sin
 
-    # what DecodeSession asks of its cache
+    # the surface shared with KVCache (see the module docstring); lens and Lcap are what DecodeSession and the messages read
+    full_step = "KV cache full: %d own slots used of %d; fork with max_new for every new token"
+    rows_refusal = None
     lens = property(lambda self: self.own_lens)
     Lcap = property(lambda self: self.Lown)
+    rows = property(lambda self: self.M)
+    room = property(lambda self: self.Lown)
 
+    def attend_step(self, layer_idx, qkv, H, D, out_width):
+        """The new row is appended to the member's own rows and attends the parent's prefix row, read in place, followed by the own rows."""
+        K.fork_rope_append(qkv, self.cos, self.sin, self.prefix_lens, self.prefix_of, self.k[layer_idx], self.v[layer_idx],
+                           self.own_lens[layer_idx], H, D)
+        return self._step_attention(qkv, self.parent.k[layer_idx], self.parent.v[layer_idx], self.k[layer_idx], self.v[layer_idx],
+                                    self.own_lens[layer_idx], H, D, out_width)
 
-@torch.no_grad()
-def fork_decode_step(model, fork, token_ids):
-    """decode_step for the members of a ForkCache: token_ids [M] -> logits [M, V] fp32.  Appends each layer's k / v at own slot own_lens[m]."""
-    if fork.filled >= fork.Lown:
-        raise RuntimeError("KV cache full: %d own slots used of %d; fork with max_new for every new token" % (fork.filled, fork.Lown))
-    fork.filled += 1
-    st = _stack(model)
-    lm = st.lm
-    x = lm.embed_tokens(token_ids.to(lm.embed_tokens.weight.device).long())          # a fresh buffer: the residual adds run on it in place
-    x = lm.each_layer(x, None, lambda i, layer, x, top: (layer.fork_decode(x, fork, i, st.use_lora), None))
-    return _lm_head(st, x)
+    def _step_attention(self, qkv, pk, pv, kc, vc, lens, H, D, out_width):
+        return K.fork_decode_attention(qkv, pk, pv, self.prefix_lens, self.prefix_of, kc, vc, lens, self.ws, H, D, out_width)
 
-
-@torch.no_grad()
-def fork_extend(model, fork, inputs_embeds, n_new):
-    """extend for the members of a ForkCache: inputs_embeds [M, n, d], n_new [M] host ints -> logits [M, V] fp32 of each member's last new
-    row (NaN where n_new[m] == 0), every check before the first launch."""
-    return _extend_rows(model, fork, inputs_embeds, n_new, "fork_extend", fork.M, fork.Lown, fork.Lown,
-                        lambda layer, x, i, n_new_d, use_lora, top: layer.fork_extend(x, fork, i, n_new_d, use_lora, top))
+    def attend_rows(self, layer_idx, qkv, n_new_d, H, D, out_width):
+        pk, pv = self.parent.k[layer_idx], self.parent.v[layer_idx]
+        kc, vc, lens = self.k[layer_idx], self.v[layer_idx], self.own_lens[layer_idx]
+        K.fork_extend_rope_append(qkv, self.cos, self.sin, self.prefix_lens, self.prefix_of, kc, vc, lens, n_new_d, H, D)
+        a = K.fork_extend_attention(qkv, pk, pv, self.prefix_lens, self.prefix_of, kc, vc, lens, n_new_d, H, D, out_width)
+        K.extend_advance(lens, n_new_d, self.Lown)
+        return a
 
 
 class BeamCache(ForkCache):
@@ -540,33 +568,37 @@ class BeamCache(ForkCache):
             raise ValueError("a BeamCache needs one group of beams per parent row (%d), got B=%r" % (parent.B, B))
         if int(num_beams) < 1:
             raise ValueError("a BeamCache needs num_beams >= 1, got %r" % (num_beams,))
-        super().__init__(parent, [b for b in range(int(B)) for _ in range(int(num_beams))], Lown, prefix_lens)
+        super().__init__(parent, n_ways(B, num_beams), Lown, prefix_lens)
         self.B, self.num_beams = int(B), int(num_beams)
         self.anc = torch.zeros(2, self.M, self.Lown, dtype=torch.int32, device=self.k[0].device)
         self.cur = 0
 
+    full_step = "KV cache full: %d own slots used of %d; allocate the BeamCache for every pushed token"
+    rows_refusal = ("a BeamCache takes one row per member and step (beam_decode_step): pushing several rows through the ancestry table is "
+                    "not implemented")
+
     @property
     def table(self):
         return self.anc[self.cur]
+
+    def _step_attention(self, qkv, pk, pv, kc, vc, lens, H, D, out_width):
+        """The own rows are read through the ancestry table (whose slot holds row t of the member's history)."""
+        return K.beam_decode_attention(qkv, pk, pv, self.prefix_lens, self.prefix_of, kc, vc, lens, self.table, self.ws, H, D, out_width)
+
+    def attend_rows(self, layer_idx, qkv, n_new_d, H, D, out_width):
+        raise NotImplementedError(self.rows_refusal)
 
 
 @torch.no_grad()
 def beam_decode_step(model, beams, token_ids, parents):
     """One step of every beam: member m pushes token_ids[m] behind the history of member parents[m] (int32 [M] on the device) -> logits
     [M, V] fp32.  One halva_beam_advance writes the other half of the ancestry table from the current one and the parents, the halves swap,
-    and the layers run: each appends its k / v at own slot own_lens[m] of member m and attends through the table."""
-    if beams.filled >= beams.Lown:
-        raise RuntimeError("KV cache full: %d own slots used of %d; allocate the BeamCache for every pushed token" % (beams.filled, beams.Lown))
-    st = _stack(model)
-    lm = st.lm
-    dev = lm.embed_tokens.weight.device
+    and decode_step runs: each layer appends its k / v at own slot own_lens[m] of member m and attends through the table."""
+    _check_room(beams)          # before the table moves: a refused step leaves cur, filled and both halves as they were
     nxt = 1 - beams.cur
-    K.beam_advance(beams.anc[beams.cur], beams.anc[nxt], parents.to(dev, torch.int32), beams.own_lens[0])
+    K.beam_advance(beams.anc[beams.cur], beams.anc[nxt], parents.to(beams.anc.device, torch.int32), beams.own_lens[0])
     beams.cur = nxt
-    beams.filled += 1
-    x = lm.embed_tokens(token_ids.to(dev).long())          # a fresh buffer: the residual adds run on it in place
-    x = lm.each_layer(x, None, lambda i, layer, x, top: (layer.beam_decode(x, beams, i, st.use_lora), None))
-    return _lm_head(st, x)
+    return decode_step(model, beams, token_ids)
 
 
 @torch.no_grad()
@@ -603,14 +635,11 @@ def sample_fork(model, inputs_embeds, seq_len, n, max_new_tokens, eos_ids, pad, 
     B, T = inputs_embeds.shape[0], inputs_embeds.shape[1]
     select = _sampler(model, B * n, inputs_embeds.device, temperature, top_k, top_p, generator)
     cache = KVCache(model, B, T, inputs_embeds.device)
-    if prefill_chunk is None:
-        logits = prefill(model, inputs_embeds, seq_len, cache)
-    else:
-        logits = prefill_chunked(model, inputs_embeds, seq_len, cache, prefill_chunk)
-    prefix_of = [b for b in range(B) for _ in range(n)]
+    logits = prompt_pass(model, inputs_embeds, seq_len, cache, prefill_chunk)
+    prefix_of = n_ways(B, n)
     fork = ForkCache(cache, prefix_of, max_new_tokens, [int(v) for v in seq_len])
     logits = logits[torch.tensor(prefix_of, dtype=torch.long, device=logits.device)]
-    return _loop_from(model, fork, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix, fork_decode_step)[0]
+    return _loop_from(model, fork, logits, max_new_tokens, eos_ids, pad, select, stopping_criteria, prefix)[0]
 
 
 class ForkedSession(DecodeSession):
@@ -622,11 +651,6 @@ class ForkedSession(DecodeSession):
         super().__init__(model, fork, logits, [0] * fork.M, config)
         self.prefix_of = list(fork.host_prefix_of)
         self.prefix_lens = [fork.host_prefix_lens[p] for p in self.prefix_of]
-
-    _step = staticmethod(lambda model, fork, tok: fork_decode_step(model, fork, tok))
-
-    def _extend(self, embeds, n_new):
-        return fork_extend(self.model, self.cache, embeds, n_new)
 
     def fork(self, n=None, prefix_of=None, max_new=256):
         raise NotImplementedError("forks of forks are not implemented; fork the parent session again")

@@ -366,19 +366,24 @@ def fork_rope_append(qkv, cos, sin, prefix_lens, prefix_of, kown, vown, own_lens
     return qkv
 
 
-def fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, ws, H, D, out_width=None, ldq=None):
-    """One query row per (member, head) over the parent keys [0, prefix_lens[p]) of row p = prefix_of[m] (pk, pv [Bp, H, Lpre, D], read in
-    place) and then the own keys [0, own_lens[m]) (kown, vown [M, H, Lown, D]) -> bf16 [M, out_width] (halva_fork_decode_attn)."""
+def _fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, anc, ws, H, D, out_width, ldq):
+    """fork_decode_attention (anc None) and beam_decode_attention (anc [M, Lown]): the checks, the output buffer and the call."""
     _chk(q, torch.bfloat16, "q"), _chk(pk, torch.bfloat16, "pk"), _chk(pv, torch.bfloat16, "pv")
     _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown")
     _chk_fork(prefix_lens, prefix_of, own_lens)
     M = q.shape[0]
     width = out_width or H * D
     out = torch.empty(M, width, dtype=torch.bfloat16, device=q.device)
-    call("halva_fork_decode_attn", ptr(q), ldq or q.shape[-1], ptr(pk), ptr(pv), ptr(prefix_lens), ptr(prefix_of), ptr(kown), ptr(vown),
-         ptr(own_lens), ptr(out), width, ptr(ws), ws.numel() * ws.element_size(), M, prefix_lens.shape[0], H, D, pk.shape[2], kown.shape[2], 0.0,
-         stream_ptr())
+    call("halva_fork_decode_attn" if anc is None else "halva_beam_decode_attn", ptr(q), ldq or q.shape[-1], ptr(pk), ptr(pv), ptr(prefix_lens),
+         ptr(prefix_of), ptr(kown), ptr(vown), ptr(own_lens), *(() if anc is None else (ptr(anc),)), ptr(out), width, ptr(ws),
+         ws.numel() * ws.element_size(), M, prefix_lens.shape[0], H, D, pk.shape[2], kown.shape[2], 0.0, stream_ptr())
     return out
+
+
+def fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, ws, H, D, out_width=None, ldq=None):
+    """One query row per (member, head) over the parent keys [0, prefix_lens[p]) of row p = prefix_of[m] (pk, pv [Bp, H, Lpre, D], read in
+    place) and then the own keys [0, own_lens[m]) (kown, vown [M, H, Lown, D]) -> bf16 [M, out_width] (halva_fork_decode_attn)."""
+    return _fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, None, ws, H, D, out_width, ldq)
 
 
 def fork_extend_rope_append(qkv, cos, sin, prefix_lens, prefix_of, kown, vown, own_lens, n_new, H, D):
@@ -410,18 +415,10 @@ def fork_extend_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_len
 # beam search over a forked cache (halva_amd/decode.py:BeamCache): the own pass of the decode attention reads through an ancestry table
 def beam_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, anc, ws, H, D, out_width=None, ldq=None):
     """fork_decode_attention with own key t of member m read from slot (anc[m][t], h, t): anc int32 [M, Lown] (halva_beam_decode_attn)."""
-    _chk(q, torch.bfloat16, "q"), _chk(pk, torch.bfloat16, "pk"), _chk(pv, torch.bfloat16, "pv")
-    _chk(kown, torch.bfloat16, "kown"), _chk(vown, torch.bfloat16, "vown"), _chk(anc, torch.int32, "anc")
-    _chk_fork(prefix_lens, prefix_of, own_lens)
-    M = q.shape[0]
-    if tuple(anc.shape) != (M, kown.shape[2]):
-        raise ValueError("beam_decode_attention: anc must be [M=%d, Lown=%d], got %s" % (M, kown.shape[2], tuple(anc.shape)))
-    width = out_width or H * D
-    out = torch.empty(M, width, dtype=torch.bfloat16, device=q.device)
-    call("halva_beam_decode_attn", ptr(q), ldq or q.shape[-1], ptr(pk), ptr(pv), ptr(prefix_lens), ptr(prefix_of), ptr(kown), ptr(vown),
-         ptr(own_lens), ptr(anc), ptr(out), width, ptr(ws), ws.numel() * ws.element_size(), M, prefix_lens.shape[0], H, D, pk.shape[2],
-         kown.shape[2], 0.0, stream_ptr())
-    return out
+    _chk(anc, torch.int32, "anc")
+    if tuple(anc.shape) != (q.shape[0], kown.shape[2]):
+        raise ValueError("beam_decode_attention: anc must be [M=%d, Lown=%d], got %s" % (q.shape[0], kown.shape[2], tuple(anc.shape)))
+    return _fork_decode_attention(q, pk, pv, prefix_lens, prefix_of, kown, vown, own_lens, anc, ws, H, D, out_width, ldq)
 
 
 def beam_advance(anc_src, anc_dst, parent, own_lens):

@@ -424,67 +424,23 @@ class DecoderLayer(nn.Module):
         return self._block(x, attend, use_lora, own_x, rows)
 
     def decode(self, x, cache, layer_idx, use_lora=True):
-        """One new token per sequence against the KV cache (halva_amd/decode.py), no autograd: x [B, d] (a buffer of the caller's own:
-        the residual adds accumulate onto it) -> [B, d].  The same pieces as forward() - the norms, the LoRA groups with their factors
-        applied unmerged, SwiGLU - with the attention replaced by RoPE + cache append and the split-KV decode kernel."""
-        kc, vc, lens = cache.k[layer_idx], cache.v[layer_idx], cache.lens[layer_idx]
-
-        def attend(qkv):
-            K.decode_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, self.H, self.D)
-            return K.decode_attention(qkv, kc, vc, lens, cache.ws, self.H, self.D, self.o.in_width)
-        return self._block(x, attend, use_lora, True, None)
+        """One new token per sequence against a KV cache (halva_amd/decode.py: a KVCache, or the members of a ForkCache / BeamCache), no
+        autograd: x [B, d] (a buffer of the caller's own: the residual adds accumulate onto it) -> [B, d].  The same pieces as forward() -
+        the norms, the LoRA groups with their factors applied unmerged, SwiGLU - with the attention replaced by the cache's attend_step:
+        RoPE + append of the new row and the split-KV decode kernel."""
+        return self._block(x, lambda qkv: cache.attend_step(layer_idx, qkv, self.H, self.D, self.o.in_width), use_lora, True, None)
 
     def extend(self, x, cache, layer_idx, n_new_d, use_lora=True, rows=None):
-        """Up to n new rows per sequence against the KV cache (halva_amd/decode.py:extend), no autograd: decode()'s body on x [B, n, d] (a
-        buffer of the caller's own) -> [B, n, d], with RoPE + append of rows i < n_new_d[b], their attention over the cache and the advance
-        of lens as three launches.  Rows i >= n_new_d[b] carry values nobody reads (every other piece is row-wise).
-        rows: as in forward() - the top layer runs its row-wise part on those flat rows of [B * n] only and returns [len(rows), d]."""
-        kc, vc, lens = cache.k[layer_idx], cache.v[layer_idx], cache.lens[layer_idx]
-
-        def attend(qkv):
-            K.extend_rope_append(qkv, cache.cos, cache.sin, kc, vc, lens, n_new_d, self.H, self.D)
-            a = K.extend_attention(qkv, kc, vc, lens, n_new_d, None, self.H, self.D, self.o.in_width)      # (its workspace is empty by design)
-            K.extend_advance(lens, n_new_d, cache.Lcap)
-            return a
-        return self._block(x, attend, use_lora, True, rows)
-
-    def fork_decode(self, x, fork, layer_idx, use_lora=True):
-        """decode() for the members of a ForkCache (halva_amd/decode.py): x [M, d]; the new row is appended to the member's own rows and
-        attends the parent's prefix row, read in place, followed by the own rows."""
-        pk, pv = fork.parent.k[layer_idx], fork.parent.v[layer_idx]
-        kc, vc, lens = fork.k[layer_idx], fork.v[layer_idx], fork.own_lens[layer_idx]
-
-        def attend(qkv):
-            K.fork_rope_append(qkv, fork.cos, fork.sin, fork.prefix_lens, fork.prefix_of, kc, vc, lens, self.H, self.D)
-            return K.fork_decode_attention(qkv, pk, pv, fork.prefix_lens, fork.prefix_of, kc, vc, lens, fork.ws, self.H, self.D, self.o.in_width)
-        return self._block(x, attend, use_lora, True, None)
-
-    def beam_decode(self, x, beams, layer_idx, use_lora=True):
-        """fork_decode() for the members of a BeamCache (halva_amd/decode.py): the same append into the member's own slot, then the attention
-        with the own rows read through the ancestry table (beams.table: whose slot holds row t of the member's history)."""
-        pk, pv = beams.parent.k[layer_idx], beams.parent.v[layer_idx]
-        kc, vc, lens = beams.k[layer_idx], beams.v[layer_idx], beams.own_lens[layer_idx]
-
-        def attend(qkv):
-            K.fork_rope_append(qkv, beams.cos, beams.sin, beams.prefix_lens, beams.prefix_of, kc, vc, lens, self.H, self.D)
-            return K.beam_decode_attention(qkv, pk, pv, beams.prefix_lens, beams.prefix_of, kc, vc, lens, beams.table, beams.ws, self.H, self.D,
-                                           self.o.in_width)
-        return self._block(x, attend, use_lora, True, None)
-
-    def fork_extend(self, x, fork, layer_idx, n_new_d, use_lora=True, rows=None):
-        """extend() for the members of a ForkCache: x [M, n, d], rows and return as there."""
-        pk, pv = fork.parent.k[layer_idx], fork.parent.v[layer_idx]
-        kc, vc, lens = fork.k[layer_idx], fork.v[layer_idx], fork.own_lens[layer_idx]
-
-        def attend(qkv):
-            K.fork_extend_rope_append(qkv, fork.cos, fork.sin, fork.prefix_lens, fork.prefix_of, kc, vc, lens, n_new_d, self.H, self.D)
-            a = K.fork_extend_attention(qkv, pk, pv, fork.prefix_lens, fork.prefix_of, kc, vc, lens, n_new_d, self.H, self.D, self.o.in_width)
-            K.extend_advance(lens, n_new_d, fork.Lown)
-            return a
-        return self._block(x, attend, use_lora, True, rows)
+        """Up to n new rows per sequence against a KV cache (halva_amd/decode.py:extend), no autograd: decode()'s body on x [B, n, d] (a
+        buffer of the caller's own) -> [B, n, d], with the cache's attend_rows: RoPE + append of rows i < n_new_d[b], their attention over
+        the cache and the advance of its lengths as three launches.  Rows i >= n_new_d[b] carry values nobody reads (every other piece is
+        row-wise).  rows: as in forward() - the top layer runs its row-wise part on those flat rows of [B * n] only and returns
+        [len(rows), d]."""
+        return self._block(x, lambda qkv: cache.attend_rows(layer_idx, qkv, n_new_d, self.H, self.D, self.o.in_width), use_lora, True, rows)
 
     def _block(self, x, attend, use_lora, own_x, rows):
-        """The decoder block, written once for forward(), decode() and extend(): attend(qkv) -> a [.., o.in_width] is all that differs."""
+        """The decoder block, written once: forward(), decode() and extend() are its three callers and attend(qkv) -> a [.., o.in_width] is
+        all that differs between them - the training attention, or what the KV cache in hand does with the projection."""
         # every producer kernel writes straight into the (wider) operand buffer of the projection that follows it
         # (norm(x), x') come out of one autograd node so that the residual's gradient is added inside the norm's backward kernel, and
         # x' is a buffer of the block's own: the o / down projections accumulate onto it (no copy of the residual)

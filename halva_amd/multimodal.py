@@ -250,10 +250,7 @@ class MultimodalMixin:
         given -> decode.DecodeSession on that cache with the last-row logits kept."""
         from . import decode as DEC
         cache = DEC.KVCache(self, embeds.shape[0], int(max_len), embeds.device)
-        if prefill_chunk is None:
-            logits = DEC.prefill(self, embeds, seq_len, cache)
-        else:
-            logits = DEC.prefill_chunked(self, embeds, seq_len, cache, prefill_chunk)
+        logits = DEC.prompt_pass(self, embeds, seq_len, cache, prefill_chunk)
         cache.filled = int(seq_len.max())
         return DEC.DecodeSession(self, cache, logits, seq_len.tolist(), self._lm_config())
 

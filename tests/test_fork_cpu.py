@@ -131,6 +131,9 @@ def _session(monkeypatch, lens, parent_scripts, member_scripts, max_len=64):
         return [[int((emb == embeds[b, i]).all(-1).nonzero()[0, 0]) for i in range(n_new[b])] for b in range(embeds.shape[0])]
 
     def fake_extend(m, c, embeds, n_new):
+        if isinstance(c, DEC.ForkCache):
+            return fake_fork_extend(m, c, embeds, n_new)
+        assert c is cache
         rec.extends.append(ids_of(embeds, n_new))
         c.lens += torch.tensor(n_new, dtype=torch.int32)
         c.filled += max(n_new)
@@ -145,15 +148,15 @@ def _session(monkeypatch, lens, parent_scripts, member_scripts, max_len=64):
         out[torch.tensor(n_new) == 0] = float("nan")
         return out
 
-    def fake_fork_step(m, f, tok):
+    def fake_step(m, f, tok):
+        if not isinstance(f, DEC.ForkCache):
+            pytest.fail("a fork must not run a step on the parent's cache")
         rec.steps.append(tok.tolist())
         f.own_lens += 1
         f.filled += 1
         return rec.logits(member_scripts, f.own_lens[0].tolist())
     monkeypatch.setattr(DEC, "extend", fake_extend)
-    monkeypatch.setattr(DEC, "fork_extend", fake_fork_extend)
-    monkeypatch.setattr(DEC, "fork_decode_step", fake_fork_step)
-    monkeypatch.setattr(DEC, "decode_step", lambda *a: pytest.fail("a fork must not run the parent's step"))
+    monkeypatch.setattr(DEC, "decode_step", fake_step)
     cfg = SimpleNamespace(eos_token_id=None, pad_token_id=None)
     ses = DEC.DecodeSession(model, cache, rec.logits(parent_scripts, list(lens)), list(lens), cfg)
     return ses, rec, cache
@@ -226,12 +229,12 @@ def test_fork_step_and_extend_checks_come_before_any_launch():
     f = DEC.ForkCache(par, [0, 1], 4, [5, 3])
     for bad in ([0, 0], [5, 1], [-1, 2], [1]):
         with pytest.raises(ValueError):
-            DEC.fork_extend(model, f, torch.zeros(2, 4, 4), bad)
+            DEC.extend(model, f, torch.zeros(2, 4, 4), bad)
     with pytest.raises(RuntimeError, match="KV cache full"):
-        DEC.fork_extend(model, f, torch.zeros(2, 5, 4), [5, 1])
+        DEC.extend(model, f, torch.zeros(2, 5, 4), [5, 1])
     f.filled = 4
     with pytest.raises(RuntimeError, match="KV cache full"):
-        DEC.fork_decode_step(model, f, torch.zeros(2, dtype=torch.long))
+        DEC.decode_step(model, f, torch.zeros(2, dtype=torch.long))
     assert f.filled == 4
 
 

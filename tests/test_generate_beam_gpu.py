@@ -36,7 +36,7 @@ def _eos_for(env, n=1):
 
 
 def _materialised(env, ses, Kb, steps, **kw):
-    """session.beam_search assembled from public pieces, with the K / V rows moved: ForkCache, fork_decode_step, an index_select of every
+    """session.beam_search assembled from public pieces, with the K / V rows moved: ForkCache, decode_step, an index_select of every
     layer's own rows by the parents before each step, kernels.beam_select, BeamState."""
     from halva_amd import decode as DEC, kernels as KR
     from halva_amd.beam import BeamState
@@ -55,7 +55,7 @@ def _materialised(env, ses, Kb, steps, **kw):
         idx = parents.cuda()
         for i in range(len(fork.k)):
             fork.k[i], fork.v[i] = fork.k[i].index_select(0, idx), fork.v[i].index_select(0, idx)
-        logits = DEC.fork_decode_step(env.model, fork, nxt.cuda())
+        logits = DEC.decode_step(env.model, fork, nxt.cuda())
     return st.finalize(), st
 
 
@@ -109,7 +109,7 @@ def test_one_beam_is_greedy(env, early):
             done[b] = t in eos
         if all(done) or s + 1 == steps:
             break
-        lg = DEC.fork_decode_step(env.model, twin.cache, nxt)
+        lg = DEC.decode_step(env.model, twin.cache, nxt)
     for b in range(B):
         n = len(toks[b])
         want = lps[b] / (n ** lp)

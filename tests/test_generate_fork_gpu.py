@@ -77,7 +77,7 @@ def test_greedy_fork_gives_the_golden_tokens_for_every_member(env):
                 assert int(lg[m].argmax()) == int(env.toks[i][s]), (m, s)
                 held[i] += m != 2
         if s + 1 < N_GOLD:
-            lg = DEC.fork_decode_step(env.model, fk.cache, torch.stack([env.toks[i][s] for i in of]).cuda())
+            lg = DEC.decode_step(env.model, fk.cache, torch.stack([env.toks[i][s] for i in of]).cuda())
     print("%s: steps held to the golden's token under teacher forcing %s of %d" % (env.name, held, N_GOLD))
     assert min(held) >= FORCED, held
     assert torch.equal(lg[1], lg[2])                      # two members with one history: the same bits
@@ -115,7 +115,7 @@ def test_sampling_with_num_return_sequences(env):
             lo = ref.cdf[tok - 1] if tok > 0 else 0.0
             assert ref.K2[tok] and lo - S.DELTA <= u[m] < ref.cdf[tok] + S.DELTA, (m, s, tok, float(u[m]), S.draw(ref.cdf, ref.K2, u[m]))
         if s + 1 < steps:
-            lg = DEC.fork_decode_step(model, fk.cache, new[:, s].cuda())
+            lg = DEC.decode_step(model, fk.cache, new[:, s].cuda())
     assert np.isfinite(l64).all()
 
 
@@ -153,12 +153,12 @@ def test_parent_appended_to_after_the_fork_leaves_the_forks_alone(env):
     tok = torch.tensor([5, 9, 11, 5, 9, 11]).cuda()
     ses = _start(env, count=2)
     fk = ses.fork(3, max_new=8)
-    want = DEC.fork_decode_step(env.model, fk.cache, tok).clone()
+    want = DEC.decode_step(env.model, fk.cache, tok).clone()
     ses2 = _start(env, count=2)
     fk2 = ses2.fork(3, max_new=8)
     ses2.append(torch.tensor([[7, 8, 9], [10, 11, 12]]))
     ses2.generate(3, eos_token_id=[])
-    got = DEC.fork_decode_step(env.model, fk2.cache, tok)
+    got = DEC.decode_step(env.model, fk2.cache, tok)
     assert torch.equal(got, want)
     assert fk2.cache.prefix_lens.tolist() == fk.cache.prefix_lens.tolist()
     assert all(a >= b + 5 for a, b in zip(ses2.lens, fk.cache.prefix_lens.tolist()))          # the parent did move on

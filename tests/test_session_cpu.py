@@ -126,7 +126,7 @@ def test_extend_checks_come_before_any_launch():
     from halva_amd import decode as DEC
     lm = SimpleNamespace(embed_tokens=torch.nn.Embedding(V, 4), layers=[])
     model = DEC.DecodeStack(lm, torch.zeros(V, 4), False)
-    cache = SimpleNamespace(B=2, Lcap=10, filled=6, cos=torch.zeros(10, 2))
+    cache = SimpleNamespace(rows=2, room=10, Lcap=10, filled=6, rows_refusal=None)
     x = torch.zeros(2, 4, 4)
     for bad in ([0, 0], [5, 1], [-1, 2], [1]):
         with pytest.raises(ValueError):
