@@ -1,4 +1,4 @@
-"""KV-cached decoding (greedy, or temperature / top-k / top-p sampling) for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) and VILA (VilaLlavaLlamaModel.generate) - forward only.
+"""KV-cached decoding (greedy, temperature / top-k / top-p sampling, or either of them contrastively against a second prompt) for LLaVA-1.5 (LlavaLlamaForCausalLM.generate) and VILA (VilaLlavaLlamaModel.generate) - forward only.
 
 Stands in for the reference's HF `generate(..., use_cache=True)` decode path: the per-layer cache concat
 (llava/model/language_model/modelling_llama.py:295-305) and the decode position rule `attention_mask.sum(1) - 1`
@@ -336,6 +336,86 @@ def _sampler(model, B, dev, temperature, top_k, top_p, generator):
         tok = K.sample_top_k_top_p(logits, u, temperature, top_k, top_p)
         return tok, tok < 0
     return select
+
+
+def check_contrast_args(has_images_cd, has_negative_ids, has_negative_mask, cd_alpha, cd_beta, guidance_scale, num_beams, num_return_sequences):
+    """generate's contrast arguments -> None when none of them is given (the call takes the plain path), else (alpha, beta) of
+    contrast().  The contrast branch is images_cd (the same ids over other images) or negative_input_ids (another prompt), not both;
+    cd_alpha (None = 0.5) >= 0 and 0 <= cd_beta (None = 0.1) <= 1 are VCD's, guidance_scale = g >= 1 is HF's alias for alpha = g - 1,
+    beta = 0.  Every refusal is a ValueError and comes before any launch: contrast with num_beams > 1 or num_return_sequences > 1, a
+    weight without a contrast branch (it would be ignored), both branches, both spellings of the weight."""
+    weights = cd_alpha is not None or cd_beta is not None or guidance_scale is not None
+    if not (has_images_cd or has_negative_ids):
+        if weights or has_negative_mask:
+            raise ValueError("generate: cd_alpha / cd_beta / guidance_scale / negative_attention_mask need a contrast branch: images_cd= or "
+                             "negative_input_ids=")
+        return None
+    if has_images_cd and has_negative_ids:
+        raise ValueError("generate: images_cd and negative_input_ids are two different contrast branches; give one of them")
+    if has_negative_mask and not has_negative_ids:
+        raise ValueError("generate: negative_attention_mask without negative_input_ids")
+    if num_beams is not None and num_beams > 1:
+        raise ValueError("generate: contrastive decoding with num_beams=%d is not supported; num_beams=1 only" % num_beams)
+    if num_return_sequences is not None and int(num_return_sequences) != 1:
+        raise ValueError("generate: contrastive decoding with num_return_sequences=%r is not supported; one sequence per prompt"
+                         % (num_return_sequences,))
+    if guidance_scale is not None:
+        if cd_alpha is not None or cd_beta is not None:
+            raise ValueError("generate: guidance_scale is an alias for cd_alpha = guidance_scale - 1, cd_beta = 0; give one spelling")
+        g = float(guidance_scale)
+        if not (g >= 1 and g != float("inf")):
+            raise ValueError("generate: guidance_scale=%r (needs a finite value >= 1)" % (guidance_scale,))
+        return g - 1.0, 0.0
+    alpha, beta = 0.5 if cd_alpha is None else float(cd_alpha), 0.1 if cd_beta is None else float(cd_beta)
+    if not (alpha >= 0 and alpha != float("inf")):
+        raise ValueError("generate: cd_alpha=%r (needs a finite value >= 0)" % (cd_alpha,))
+    if not 0 <= beta <= 1:
+        raise ValueError("generate: cd_beta=%r (needs 0 <= cd_beta <= 1)" % (cd_beta,))
+    return alpha, beta
+
+
+@torch.no_grad()
+def contrast(model, inputs_embeds, seq_len, embeds_cd, seq_len_cd, max_new_tokens, eos_ids, pad, alpha, beta, sampling=None, generator=None,
+             stopping_criteria=None, prefix=None, prefill_chunk=None):
+    """Contrastive decoding (VCD; classifier-free guidance with beta = 0): as greedy() / sample(), with each step's token chosen from
+    (1 + alpha) * logits - alpha * logits_cd over the columns plausible under logits (kernels.contrast_select, ONE native launch) ->
+    LongTensor [B, n].  The prompt as given (inputs_embeds [B, T, d], seq_len) and the contrast prompt (embeds_cd [B, T', d], seq_len_cd)
+    share one KVCache of 2 B rows - rows [0, B) the former, rows [B, 2 B) the latter, right-padded to a common T - one prompt pass and one
+    decode step per token: both rows of a pair push the same token.  sampling: None = greedy contrast (the lowest index among the maxima),
+    or (temperature, top_k, top_p) with u = torch.rand(B, generator=generator) drawn exactly once per step, done rows included.
+    stopping_criteria see the B rows of the prompt as given, with `prefix` in front."""
+    B, T = inputs_embeds.shape[0], max(inputs_embeds.shape[1], embeds_cd.shape[1])
+    if embeds_cd.shape[0] != B or embeds_cd.shape[2] != inputs_embeds.shape[2]:
+        raise ValueError("contrast: the contrast prompt needs the prompt's batch and width %s, got %s"
+                         % ((B, inputs_embeds.shape[2]), (embeds_cd.shape[0], embeds_cd.shape[2])))
+    V = _stack(model).lm_head.shape[0]
+    if V > K.sample_max_vocab():
+        raise ValueError("generate: contrastive decoding takes a vocabulary of at most %d entries, the head has %d" % (K.sample_max_vocab(), V))
+    dev = inputs_embeds.device
+    both = torch.zeros(2 * B, T, inputs_embeds.shape[2], dtype=inputs_embeds.dtype, device=dev)
+    both[:B, :inputs_embeds.shape[1]] = inputs_embeds
+    both[B:, :embeds_cd.shape[1]] = embeds_cd.to(dev, inputs_embeds.dtype)
+    lens = torch.cat([torch.as_tensor(seq_len, dtype=torch.int32).view(-1).cpu(), torch.as_tensor(seq_len_cd, dtype=torch.int32).view(-1).cpu()])
+    temperature, top_k, top_p = (1.0, 1, 1.0) if sampling is None else sampling
+    zeros = torch.zeros(B, dtype=torch.float32, device=dev)
+
+    def select(logits):
+        u = zeros if sampling is None else torch.rand(B, device=dev, generator=generator)
+        tok = K.contrast_select(logits[:B], logits[B:], u, alpha, beta, temperature, top_k, top_p)
+        return tok.repeat(2), (tok < 0).repeat(2)
+
+    crits = [] if stopping_criteria is None else ([stopping_criteria] if callable(stopping_criteria) else list(stopping_criteria))
+
+    def first_half(crit):
+        def on_pairs(seq, logits):
+            stop = crit(seq[:B] if prefix is None else torch.cat([prefix, seq[:B]], 1), logits[:B])
+            return stop.to(dev, torch.bool).view(-1).expand(B).repeat(2) if isinstance(stop, torch.Tensor) else stop
+        return on_pairs
+
+    cache = KVCache(model, 2 * B, T + max_new_tokens, dev)
+    logits = prompt_pass(model, both, lens, cache, prefill_chunk)
+    out, _ = _loop_from(model, cache, logits, max_new_tokens, eos_ids, pad, select, [first_half(c) for c in crits] or None, None)
+    return out[:B]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -79,6 +79,7 @@ SIGNATURES = {
     "halva_beam_select_max_candidates": [],
     "halva_sample_top_k_top_p": [_P, _L, _P, _P, _P, _P, _I, _I, _F, _I, _F, _P],
     "halva_sample_max_vocab": [],
+    "halva_contrast_select": [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _I, _F, _P],
 }
 
 

@@ -489,6 +489,36 @@ def sample_top_k_top_p(logits, u, temperature, top_k, top_p, want_diag=False):
     return (token, thr, kept) if want_diag else token
 
 
+def contrast_select(logits, logits_cd, u, alpha, beta, temperature, top_k, top_p, want_diag=False):
+    """One token per row pair of fp32 logits / logits_cd [B, V] (unit column stride, each with any row stride >= V): x = (1 + alpha) *
+    logits - alpha * logits_cd on the columns with logits >= max(logits) + log(beta), -inf elsewhere, then temperature / top-k / top-p and the
+    draw with the caller's u [B] as sample_top_k_top_p does them on x (include/halva_hip.h:halva_contrast_select) -> token int64 [B]; with
+    want_diag also the threshold on x / temperature (fp32 [B]), the size of the kept set and the number of plausible columns (int32 [B]
+    each).  A row that cannot be served gives -1."""
+    _chk(u, torch.float32, "u")
+    for name, t in (("logits", logits), ("logits_cd", logits_cd)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 device tensor, got %s on %s" % (name, t.dtype, t.device))
+        if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise ValueError("contrast_select: %s [B, V] with unit column stride; got %s %s" % (name, tuple(t.shape), t.stride()))
+    if logits.shape != logits_cd.shape or logits.device != logits_cd.device or u.shape != (logits.shape[0],):
+        raise ValueError("contrast_select: logits and logits_cd of one shape on one device and contiguous u [B]; got %s, %s and %s"
+                         % (tuple(logits.shape), tuple(logits_cd.shape), tuple(u.shape)))
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError("contrast_select: beta=%r (needs 0 <= beta <= 1)" % beta)
+    B, V = logits.shape
+    dev = logits.device
+    token = torch.empty(B, dtype=torch.int64, device=dev)
+    thr = torch.empty(B, dtype=torch.float32, device=dev) if want_diag else None
+    kept = torch.empty(B, dtype=torch.int32, device=dev) if want_diag else None
+    plausible = torch.empty(B, dtype=torch.int32, device=dev) if want_diag else None
+    call("halva_contrast_select", ptr(logits), logits.stride(0), ptr(logits_cd), logits_cd.stride(0), ptr(u), ptr(token), ptr(thr), ptr(kept),
+         ptr(plausible), B, V, float(alpha), math.log(beta) if beta > 0 else -math.inf, float(temperature), int(top_k), float(top_p),
+         stream_ptr())
+    return (token, thr, kept, plausible) if want_diag else token
+
+
 def sdpa_full(qkv, H, D, scale=0.0):
     """Non-causal attention of the frozen CLIP / SigLIP tower (forward only).  qkv [N, S, 3*H*D] -> [N, S, H*D].
     scale 0 = 1/sqrt(D); SigLIP's 72-wide heads run zero-padded to D=128 with scale = 72**-0.5."""

@@ -227,18 +227,26 @@ class LlavaLlamaForCausalLM(nn.Module, LlavaMetaForCausalLM):
 
     def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
                  max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, image_sizes=None,
-                 top_k=None, generator=None, prefill_chunk=None, num_return_sequences=1, **unused):
+                 top_k=None, generator=None, prefill_chunk=None, num_return_sequences=1, images_cd=None,
+                 negative_input_ids=None, negative_attention_mask=None, cd_alpha=None, cd_beta=None, guidance_scale=None, **unused):
         """Decoding with a KV cache: the calls of the reference's hallucination benchmarks.  Greedy
         (eval_hall/model_vqa_loader.py etc.: do_sample=False, temperature=0, num_beams=1, use_cache=True), or, with do_sample=True and a
         temperature > 0 (eval_hall/model_chair_loader.py:124-130), sampling under temperature / top_k (None = 50, HF's default; 0 = off) /
         top_p (None = 1.0) with the random numbers of `generator` (a device torch.Generator; None = the default one);
         num_return_sequences = n > 1 (sampling only) gives n continuations per prompt over one prompt pass and a forked cache, rows
         b * n + i with the prompt repeated.
+        Contrastive decoding (halva_amd/decode.py:contrast): images_cd= (the same ids over other images, e.g. contrast.add_diffusion_noise
+        of `images`: visual contrastive decoding) or negative_input_ids= / negative_attention_mask= (another prompt: classifier-free
+        guidance) adds a second row per prompt, and each token is chosen, greedily or sampled as do_sample says, from (1 + cd_alpha) *
+        logits - cd_alpha * logits_cd over the tokens whose probability under the prompt as given is at least cd_beta times the largest
+        (cd_alpha None = 0.5, cd_beta None = 0.1; guidance_scale=g is cd_alpha = g - 1, cd_beta = 0).  num_beams > 1 or
+        num_return_sequences > 1 with it is a ValueError.
         input_ids [B, T] (IMAGE_TOKEN_INDEX marks the image; right-padded batches carry attention_mask), images [B, 3, H, W]
         (fp16 accepted).  Returns LongTensor [B, T + n]: the prompt as given, then the new tokens; a row that emitted EOS is padded
         with pad_token_id after it.  Stops when every row is done or after max_new_tokens; one host sync per step."""
         return self._generate(input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                              stopping_criteria, temperature, top_k, top_p, generator, prefill_chunk, num_return_sequences)
+                              stopping_criteria, temperature, top_k, top_p, generator, prefill_chunk, num_return_sequences, images_cd,
+                              negative_input_ids, negative_attention_mask, cd_alpha, cd_beta, guidance_scale)
 
     __call__ = nn.Module.__call__
 

@@ -216,12 +216,18 @@ class MultimodalMixin:
 
     @torch.no_grad()
     def _generate(self, input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None, prefill_chunk=None, num_return_sequences=1):
+                  stopping_criteria, temperature=None, top_k=None, top_p=None, generator=None, prefill_chunk=None, num_return_sequences=1,
+                  images_cd=None, negative_input_ids=None, negative_attention_mask=None, cd_alpha=None, cd_beta=None, guidance_scale=None):
         """The body of `generate`: _embed_prompt, then halva_amd/decode.py:greedy, or :sample when do_sample is set.  prefill_chunk: None =
         one prompt pass; an int >= 1 = the prompt pass in blocks of that many rows (decode.prefill_chunked).  num_return_sequences = n > 1
         (sampling only, as in HF): one prompt pass, then n continuations per prompt over a forked cache (decode.sample_fork) -> rows
-        b * n + i, with the prompt repeated where the prompt is returned."""
+        b * n + i, with the prompt repeated where the prompt is returned.  images_cd (the same ids over other images) or negative_input_ids
+        / negative_attention_mask (another prompt; its image tokens, if any, take `images`) turn on contrastive decoding
+        (decode.contrast) with cd_alpha (None = 0.5) and cd_beta (None = 0.1), or guidance_scale = 1 + alpha with beta = 0; without them the
+        call runs exactly as before."""
         from . import decode as DEC
+        cd = DEC.check_contrast_args(images_cd is not None, negative_input_ids is not None, negative_attention_mask is not None, cd_alpha,
+                                     cd_beta, guidance_scale, num_beams, num_return_sequences)
         sampling = DEC.check_generate_args(num_beams, do_sample, max_new_tokens, temperature, top_k, top_p)
         n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
         if n_ret < 1:
@@ -234,7 +240,17 @@ class MultimodalMixin:
         dev = self.device
         eos_ids, pad = DEC.eos_and_pad(self._lm_config(), eos_token_id, pad_token_id, dev)
         prompt = input_ids.to(dev) if self.generate_returns_prompt else None
-        if n_ret > 1:
+        if cd is not None:
+            if images_cd is not None:
+                embeds_cd, seq_len_cd = self._embed_prompt(input_ids, images_cd, attention_mask)
+            else:
+                if negative_input_ids.ndim != 2 or negative_input_ids.shape[0] != input_ids.shape[0]:
+                    raise ValueError("generate: negative_input_ids needs one row per prompt [B=%d, T']" % input_ids.shape[0])
+                embeds_cd, seq_len_cd = self._embed_prompt(negative_input_ids, images if bool((negative_input_ids < 0).any()) else None,
+                                                           negative_attention_mask)
+            out = DEC.contrast(self, embeds, seq_len, embeds_cd, seq_len_cd, max_new_tokens, eos_ids, pad, *cd, sampling=sampling,
+                               generator=generator, stopping_criteria=stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)
+        elif n_ret > 1:
             prompt = None if prompt is None else prompt.repeat_interleave(n_ret, 0)
             out = DEC.sample_fork(self, embeds, seq_len, n_ret, max_new_tokens, eos_ids, pad, *sampling, generator=generator,
                                   stopping_criteria=stopping_criteria, prefix=prompt, prefill_chunk=prefill_chunk)

@@ -359,12 +359,15 @@ class VilaLlavaLlamaModel(nn.Module, MultimodalMixin):
     # -- generation (llava_llama.py:180-206) ------------------------------------------------------
     def generate(self, input_ids=None, images=None, attention_mask=None, do_sample=False, temperature=None, top_p=None, num_beams=1,
                  max_new_tokens=128, use_cache=True, eos_token_id=None, pad_token_id=None, stopping_criteria=None, top_k=None,
-                 generator=None, prefill_chunk=None, num_return_sequences=1, **unused):
+                 generator=None, prefill_chunk=None, num_return_sequences=1, images_cd=None,
+                 negative_input_ids=None, negative_attention_mask=None, cd_alpha=None, cd_beta=None, guidance_scale=None, **unused):
         """Decoding with a KV cache: the call of the reference's VILA hallucination benchmarks (eval_hall_vila/*: do_sample=False,
         temperature=0, num_beams=1, use_cache=True, stopping_criteria None or [KeywordsStoppingCriteria]) decodes greedily; do_sample=True
         with a temperature > 0 samples under temperature / top_k (None = 50, HF's default; 0 = off) / top_p (None = 1.0) with the random
         numbers of `generator` (a device torch.Generator; None = the default one); num_return_sequences = n > 1 (sampling only) gives n
         continuations per prompt over one prompt pass and a forked cache, rows b * n + i.
+        Contrastive decoding: images_cd=, negative_input_ids= / negative_attention_mask=, cd_alpha=, cd_beta=, guidance_scale= as in
+        LlavaLlamaForCausalLM.generate (halva_amd/decode.py:contrast).
         input_ids [B, T] (IMAGE_TOKEN_INDEX marks each image; right-padded batches carry attention_mask); images [B, 3, H, W], a list of
         them or [B, n, 3, H, W] (fp16 accepted).  The splice is prepare_inputs_labels_for_multimodal's; the prompt pass and the decode
         steps run on `.llm` (halva_amd/decode.py:greedy / sample).
@@ -375,7 +378,8 @@ class VilaLlavaLlamaModel(nn.Module, MultimodalMixin):
         or after max_new_tokens.  stopping_criteria (a callable or a list of them; any True stops the batch) see the new tokens only,
         as HF hands them over for inputs_embeds generation."""
         return self._generate(input_ids, images, attention_mask, do_sample, num_beams, max_new_tokens, eos_token_id, pad_token_id,
-                              stopping_criteria, temperature, top_k, top_p, generator, prefill_chunk, num_return_sequences)
+                              stopping_criteria, temperature, top_k, top_p, generator, prefill_chunk, num_return_sequences, images_cd,
+                              negative_input_ids, negative_attention_mask, cd_alpha, cd_beta, guidance_scale)
 
 
 def _load_tokenizer(llm_path, model_max_length):

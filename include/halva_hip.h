@@ -433,6 +433,31 @@ int halva_sample_top_k_top_p(const float* logits, int64_t ld, const float* u, in
                              float temperature, int top_k, float top_p, void* stream);
 int halva_sample_max_vocab(void);
 
+/* ---- Contrastive decoding (generate with images_cd= / negative_input_ids= / guidance_scale=, halva_amd/decode.py:contrast).  One launch for
+ * the per-step token rule of visual contrastive decoding (Leng et al., "Mitigating Object Hallucinations in Large Vision-Language Models
+ * through Visual Contrastive Decoding", CVPR 2024, eqs. 3 and 4: logits of the prompt as given against logits of the prompt with a degraded
+ * image, under an adaptive plausibility constraint) and of classifier-free guidance as HF's generate runs it
+ * (transformers/generation/logits_process.py:UnbatchedClassifierFreeGuidanceLogitsProcessor, guidance_scale = 1 + alpha, beta = 0), followed
+ * by the warpers and the draw of halva_sample_top_k_top_p.
+ *   logits, logits_cd fp32 [B, V] with row strides ld, ld_cd >= V elements (columns [V, ld) are never read); u as in
+ *   halva_sample_top_k_top_p; alpha >= 0, finite; log_beta = log(beta) <= 0, -inf for beta = 0; temperature, top_k, top_p as there.
+ * Per row, in fp32, each operation rounded once and none fused (float32 arithmetic on the host gives the same bits):
+ *   m = max_i l_i;  cut = m + log_beta;  x_i = -inf where l_i < cut, else (1 + alpha) * l_i - alpha * lcd_i as product, product, difference,
+ *   1 + alpha being formed once on the host as a float.
+ * From x on the rule is halva_sample_top_k_top_p's with x in place of the logits: / temperature, K1, K2, ties kept at both cuts, the draw,
+ * the same fixed reduction orders.  top_k = 1, top_p = 1, temperature = 1, u = 0 is greedy contrast: the lowest index among the maxima of x.
+ * The raw-logit rule (VCD) and the log-softmax rule (HF: g * (s - s_u) + s_u) differ by a constant per row, hence in nothing that is
+ * returned but thr, which is on this x.
+ * A masked column's lcd does not matter: it is masked before x is formed, so a NaN or an inf there changes nothing.
+ * token int64 [B]; thr fp32 [B] (the threshold on x / temperature), kept int32 [B] (|K2|) and plausible int32 [B] (#{ i : l_i >= cut }) are
+ * diagnostics, NULL allowed.  token -1, kept 0, thr NaN for a row where l holds a NaN or +inf or nothing above -inf (plausible 0; lcd is not
+ * read), where lcd holds a NaN or +inf in a column that is not masked, or where x holds a NaN or +inf (-inf - -inf; lcd = -inf with
+ * alpha > 0); other rows are unaffected.  No float atomics; row b's outputs are bitwise the same in any batch, at any row position and with
+ * any strides.  Each row is read from HBM once.  V <= halva_sample_max_vocab(); anything else is HALVA_ERR_INVALID_ARG. */
+int halva_contrast_select(const float* logits, int64_t ld, const float* logits_cd, int64_t ld_cd, const float* u, int64_t* token, float* thr,
+                          int32_t* kept, int32_t* plausible, int B, int V, float alpha, float log_beta, float temperature, int top_k,
+                          float top_p, void* stream);
+
 /* ---- hardware-layout probes used by the GPU tests (MFMA fragment maps, ds_read_b64_tr_b16). */
 int halva_probe_layouts(int32_t* out, int n, void* stream);
 /* ---- measurement aid (bench.py's clock trace; no reference counterpart): `blocks` one-wave workgroups each spin for `spin_ticks` ticks of

@@ -34,10 +34,16 @@ candidates - on the fp32 logits that are timed, on the same logits rounded to bf
 row), with every differing place and its float64 score gap.
 With the model: `loop`, ms/step of the beam loop beside the greedy loop on the same prompts.  Measurement only, no gate.
 
-    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--fork] [--beam] [--out profiles/r07_decode.json] [--steps 32]
+--contrast: the record gains `contrast`: at V = 32000 and B = 1 and 16, us per call of the contrast select (halva_contrast_select) beside
+halva_sample_top_k_top_p on one of its two inputs and beside the torch composition of the same rule (max, compare, two products, a
+difference, masked_fill, then torch_select) - and, with the model, ms per step of the contrast loop (decode.contrast: 2 B rows) beside the
+greedy loop at B on the same prompts.  Measurement only, no gate.  Without --out it writes profiles/r14_contrast.json.
+
+    python tools/bench_decode.py [--model llava7b | vila13b] [--merged] [--sample] [--extend] [--fork] [--beam] [--contrast] [--out profiles/r07_decode.json] [--steps 32]
 """
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -209,6 +215,72 @@ def loop_numbers(m, steps, text=64, image=336):
         res["B%d" % B] = {"greedy_ms_per_step": round((wall(greedy, steps + 1) - wall(greedy, 1)) / steps, 3),
                           "sampled_ms_per_step": round((wall(sampled, steps + 1) - wall(sampled, 1)) / steps, 3)}
     return {"temperature": T_, "top_k": k, "top_p": p, "loop": res}
+
+
+CONTRAST = (0.5, 0.1)          # (alpha, beta): VCD's defaults
+
+
+def torch_contrast_select(logits, logits_cd, alpha, beta, temperature, top_k, top_p):
+    """halva_contrast_select's rule composed in torch, then torch_select."""
+    cut = logits.max(-1, keepdim=True)[0] + math.log(beta)
+    x = ((1 + alpha) * logits - alpha * logits_cd).masked_fill(logits < cut, -float("inf"))
+    return torch_select(x, temperature, top_k, top_p)
+
+
+def contrast_select_numbers(V=32000, reps=200):
+    from halva_amd import kernels as K
+    alpha, beta = CONTRAST
+    res = {}
+    for B in (1, 16):
+        logits = (8.0 * torch.randn(B, V, device="cuda")).bfloat16().float()
+        logits_cd = (logits + 2.0 * torch.randn(B, V, device="cuda")).bfloat16().float()
+        u = torch.rand(B, device="cuda")
+        for T, k, p in SAMPLE_SETTINGS:
+            native = _time(lambda: K.contrast_select(logits, logits_cd, u, alpha, beta, T, k, p), reps, warmup=10)
+            plain = _time(lambda: K.sample_top_k_top_p(logits, u, T, k, p), reps, warmup=10)
+            composed = _time(lambda: torch_contrast_select(logits, logits_cd, alpha, beta, T, k, p), reps, warmup=10)
+            res["B%d_T%g_k%d_p%g" % (B, T, k, p)] = {"contrast_us": round(native * 1e3, 2), "sample_us": round(plain * 1e3, 2),
+                                                     "torch_us": round(composed * 1e3, 2)}
+    return {"V": V, "alpha": alpha, "beta": beta, "by_setting": res}
+
+
+def contrast_loop_numbers(m, steps, text=64, image=336):
+    """ms per step of the greedy contrast loop (2 B rows in one cache) beside the greedy loop at B, host syncs included."""
+    import time
+    from halva_amd import decode as DEC
+    from halva_amd.contrast import add_diffusion_noise
+    g = torch.Generator().manual_seed(0)
+    alpha, beta = CONTRAST
+    none = torch.empty(0, dtype=torch.long, device="cuda")
+    res = {}
+    for B in (1, 16):
+        ids = torch.randint(3, 32000, (B, text), generator=g)
+        ids[:, 0] = 1
+        ids[:, 6] = -200
+        images = torch.randn(B, 3, image, image, generator=g).to("cuda", torch.bfloat16)
+        with torch.no_grad():
+            embeds, plan = m._splice(ids.cuda(), None, None, None, images)
+            embeds_cd, plan_cd = m._splice(ids.cuda(), None, None, None, add_diffusion_noise(images, 500))
+
+        def wall(fn, n):
+            best = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(n)
+                torch.cuda.synchronize()
+                best.append(time.perf_counter() - t0)
+            return statistics.median(best) * 1e3
+
+        def greedy(n):
+            DEC.greedy(m, embeds, plan.seq_len, n, none, 0)
+
+        def contrast(n):
+            DEC.contrast(m, embeds, plan.seq_len, embeds_cd, plan_cd.seq_len, n, none, 0, alpha, beta)
+        greedy(2), contrast(2)
+        res["B%d" % B] = {"greedy_ms_per_step": round((wall(greedy, steps + 1) - wall(greedy, 1)) / steps, 3),
+                          "contrast_ms_per_step": round((wall(contrast, steps + 1) - wall(contrast, 1)) / steps, 3)}
+    return res
 
 
 def extend_kernel_numbers(H=32, D=128, T=639, n2=32, reps=20):
@@ -528,7 +600,12 @@ def main():
     ap.add_argument("--beam", action="store_true",
                     help="also time the beam decode attention beside the fork attention (identity table), halva_beam_advance beside the "
                          "index_select it replaces, halva_beam_select beside log_softmax + topk, and the beam loop beside the greedy loop")
+    ap.add_argument("--contrast", action="store_true",
+                    help="also time the contrast select beside the plain select and its torch composition, and the contrast loop (2 B rows) "
+                         "beside the greedy loop")
     a = ap.parse_args()
+    if a.contrast and a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r14_contrast.json")
     from halva_amd import hip
     hip.load()
     torch.cuda.set_device(0)
@@ -537,6 +614,8 @@ def main():
            "decode_attn": attn_kernel(H=40, L=4096) if vila else attn_kernel()}
     if a.sample:
         rec["sample"] = select_numbers()
+    if a.contrast:
+        rec["contrast"] = contrast_select_numbers()
     if a.extend:
         rec["extend"] = extend_kernel_numbers()
     if a.fork:
@@ -554,6 +633,8 @@ def main():
         rec["decode"] = numbers()
         if a.sample:
             rec["sample"].update(loop_numbers(m, a.steps, text=60, image=384) if vila else loop_numbers(m, a.steps))
+        if a.contrast:
+            rec["contrast"]["loop"] = contrast_loop_numbers(m, a.steps, text=60, image=384) if vila else contrast_loop_numbers(m, a.steps)
         if a.extend:
             rec["extend"]["second_turn"] = extend_turn_numbers(m, text=60, image=384) if vila else extend_turn_numbers(m)
         if a.fork:
