@@ -1,6 +1,6 @@
-// The split-KV partial of ONE query row over ONE chunk of KC keys - the one routine behind decode_attn_partial_kernel (decode.hip: the
-// chunk of sequence b's cache) and the two partial passes of fork.hip (a chunk of a shared prefix row, held in registers once and served
-// to every member of the workgroup's block; a chunk of a member's own rows).  The per-key arithmetic, the order of every sum and the
+// The split-KV partial of ONE query row over ONE chunk of KC keys - the one routine behind the two partial passes of kvcache.hip
+// (own_partial_kernel: a chunk of a row's own keys; prefix_partial_kernel: a chunk of a shared prefix row, held in registers once and
+// served to every member of the workgroup's block).  The per-key arithmetic, the order of every sum and the
 // record (m, l, o[128]) are therefore the same wherever a chunk is reduced.
 #pragma once
 #include "common.h"
@@ -32,7 +32,7 @@ struct DecChunkRegs {
         }
     }
     // As load(), with key t of the (member, head) row fetched from the slot of ANOTHER member: anc_row[t] names the member whose own slot t
-    // holds the row (beam search's ancestry table, fork.hip:beam_own_partial_kernel).  kbase / vbase: the [M, H, Lown, 128] caches + this
+    // holds the row (beam search's ancestry table, kvcache.hip:own_partial_kernel<256, true>).  kbase / vbase: the [M, H, Lown, 128] caches + this
     // lane's piece.  The 16 lanes of a key row read the same word of anc_row; the lane's NI words are loaded first, then all K, then all V.
     // The member index is clamped into [0, M): whatever the table holds, no address leaves the allocation.
     __device__ __forceinline__ void load_via(const u32x4* __restrict__ kbase, const u32x4* __restrict__ vbase, const int32_t* __restrict__ anc_row,

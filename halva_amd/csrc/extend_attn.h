@@ -1,5 +1,5 @@
-// Causal attention of a block of new rows over a kept KV cache on MFMA - the one kernel body behind extend_attn_kernel (extend.hip) and
-// fork_extend_attn_kernel (fork.hip: the same walk with the 64-key tiles of a shared prefix row in front).  Included inside the
+// Causal attention of a block of new rows over a kept KV cache on MFMA - the kernel body behind rows_attn_kernel (kvcache.hip; for a
+// fork, the same walk with the 64-key tiles of a shared prefix row in front).  Included inside the
 // translation unit's anonymous namespace, behind sdpa_common.h.
 #pragma once
 

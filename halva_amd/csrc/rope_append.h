@@ -1,5 +1,5 @@
-// RoPE + KV-cache append of ONE qkv row - the one routine behind decode_rope_append_kernel (decode.hip: the row of sequence b at
-// position lens[b]) and extend_rope_append_kernel (extend.hip: row i of sequence b at position lens[b] + i).
+// RoPE + KV-cache append of ONE qkv row - the one routine behind rope_append_kernel (kvcache.hip: the step's row of sequence b at
+// position lens[b], or row i of a block of rows at position lens[b] + i; behind a prefix, the tables come shifted by its length).
 #pragma once
 #include "common.h"
 

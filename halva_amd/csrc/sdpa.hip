@@ -22,7 +22,7 @@
 //   sdpa_bwd_dq_kernel         sdpa_bwd_dq.h     the 3-product dQ (forms delta itself): head_dim 64 and calls without a workspace, in front of sdpa_bwd_dkv2
 // sdpa_common.h holds what they share: SdpaParams, the branch mask, LDS tiles (one XOR swizzle, conflict-free for ds_read_b128 row reads
 // and transposed reads) and their LDS-DMA, the softmax pieces of a score tile (mask_half, half_max, xhalf_max / xhalf_sum, kRescaleAt: also
-// what extend.hip's attention uses), the store epilogues (with the inverse RoPE), the block maps.
+// what the rows attention of kvcache.hip uses), the store epilogues (with the inverse RoPE), the block maps.
 // No atomics on results: dQ has its own kernels, so results are bitwise reproducible.
 // Each kernel is compiled ONE way: the only -D switches are HALVA_STAMP / HALVA_STAMP_STRIDE (the in-kernel clock); the variants that were
 // measured and retired are described in DESIGN.md 5.3.

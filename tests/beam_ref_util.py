@@ -1,4 +1,4 @@
-"""Host-side helpers for the beam-search tests (halva_amd/beam.py, halva_amd/csrc/beam.hip, the beam entries of csrc/fork.hip), torch only.
+"""Host-side helpers for the beam-search tests (halva_amd/beam.py, halva_amd/csrc/beam.hip, the beam entries of csrc/kvcache.hip and csrc/fork.hip), torch only.
 
   select_reference   halva_beam_select in float64: per prompt the C best of beam_scores[k] + log_softmax(logits[k])[i], descending, ties
                      by the lower flat index k * V + i; also the C + 1-th score (for the gap condition) and each row's lse.

@@ -6,7 +6,7 @@ append); key j is visible to new row i iff j <= past + i.  Everything is compute
   reference   float64 softmax(q K^T / sqrt(D)) V.
   model       the rounding model of tests/test_sdpa_rowwise_gpu.py's `out`: fp32 scores in the log2 domain, the TRUE row maximum, P rounded to
               bf16 before P V, the output rounded to bf16.
-  emulate     the arithmetic csrc/extend.hip documents, restated plainly: 64-key tiles from key 0, per row an exponent reference m_ref that
+  emulate     the arithmetic csrc/extend_attn.h documents, restated plainly: 64-key tiles from key 0, per row an exponent reference m_ref that
               moves iff the row's tile maximum exceeds it by more than 64 log2 units (old sum and old O scaled by exp2(m_ref - m_next) at a
               move), P = exp2(s - m_ref) rounded to bf16 for P V, the fp32 sum over the unrounded P.  Never compared with the kernel bit for
               bit: it exists so that test inputs can be shown admissible (and the bound shown to discriminate) without a GPU.
@@ -19,7 +19,7 @@ import math
 import torch
 
 C_OUT, F_OUT, G_OUT = 2.0, 2.0 ** -8, 2.0 ** -14      # tests/test_sdpa_rowwise_gpu.py: C_X["out"], F_X["out"], G_X["out"]
-BM, WAVE_ROWS, BN = 128, 32, 64                       # csrc/extend.hip: query rows per workgroup and per wave, keys per tile
+BM, WAVE_ROWS, BN = 128, 32, 64                       # csrc/extend_attn.h: query rows per workgroup and per wave, keys per tile
 RESCALE_AT = 64.0                                     # log2 units (kRescaleAt, sdpa_common.h)
 LOG2E = 1.4426950408889634
 WIDE_PROFILES = ("up", "down", "spike_late", "spike_first", "flat")
@@ -93,12 +93,12 @@ def row_bound(err_model, ref_norm):
 
 # ------------------------------------------------------------------------------------------------
 def ext_rows(past, n_new, n, Lcap):
-    """csrc/extend.hip:ext_rows - n_new cut to [0, n] and to the free slots of the cache."""
+    """csrc/extend_attn.h:ext_rows - n_new cut to [0, n] and to the free slots of the cache."""
     return max(min(min(n_new, n), Lcap - past), 0)
 
 
 def layout_classes(past, n_new, n, Lcap):
-    """The paths extend_attn_kernel takes for one sequence, as a set of tuples:
+    """The paths rows_attn_kernel takes for one sequence, as a set of tuples:
       ("blocks", k)            k live query blocks (0: the sequence returns early)
       ("last_waves", w)        live waves of the last live block
       ("dead_wave", later)     a live block with a dead trailing wave; later = the block is not the first

@@ -1,4 +1,4 @@
-"""Host-side helpers for the fork tests (halva_amd/csrc/fork.hip, halva_amd/decode.py:ForkCache), torch only, any device.
+"""Host-side helpers for the fork tests (halva_amd/csrc/kvcache.hip, halva_amd/decode.py:ForkCache), torch only, any device.
 
 A member's keys are the first plen rows of its prefix row followed by its own rows, so every reference here is extend_ref_util's on the
 concatenated keys: nothing new is modelled.  tests/test_fork_cpu.py checks the float64 decode reference against extend_ref_util.reference.
@@ -14,7 +14,7 @@ import torch
 import extend_ref_util as E
 
 GUARD, SENTINEL = 4096, 7.5
-KC, BLOCK = 256, 16          # csrc/fork.hip: keys per split-KV chunk, members served from one prefix load
+KC, BLOCK = 256, 16          # csrc/kvcache.hip: keys per split-KV chunk, members served from one prefix load
 
 
 def decode_tol(ref):

@@ -1,4 +1,4 @@
-"""The beam-search kernels alone (halva_amd/csrc/beam.hip; beam_own_partial_kernel and beam_advance_kernel of csrc/fork.hip): H = 2, D = 128.
+"""The beam-search kernels alone (halva_amd/csrc/beam.hip; the table-reading own pass of csrc/kvcache.hip, beam_advance_kernel of csrc/fork.hip): H = 2, D = 128.
 
 halva_beam_select against tests/beam_ref_util.py's float64 reference on inputs whose float64 top C + 1 per prompt are more than 1e-3 apart
 (asserted on the host): tokens and beams exactly, scores within beam_ref_util.select_bound; the tie rule, the -1 rule, row independence,

@@ -1,4 +1,4 @@
-"""The kernels that extend a kept KV cache by a block of rows (halva_amd/csrc/extend.hip: halva_extend_rope_append, halva_extend_attn,
+"""The kernels that extend a kept KV cache by a block of rows (halva_amd/csrc/kvcache.hip: halva_extend_rope_append, halva_extend_attn,
 halva_extend_advance), alone: H = 2, D = 128, Lcap = 320.
 
 past = [0, 37, 130, 255], n_new = [65, 1, 33, 64], n = 65: key counts on both sides of the 64- and 256-boundaries, query blocks of 1, 32 + 1

@@ -1,4 +1,4 @@
-"""The fork kernels (halva_amd/csrc/fork.hip) alone: H = 2, D = 128.
+"""The fork kernels (the fork entries of halva_amd/csrc/kvcache.hip) alone: H = 2, D = 128.
 
 Decode attention (halva_fork_decode_attn) per element against float64 under the tolerance tests/test_decode_kernels_gpu.py holds
 halva_decode_attn to, |err| <= 2^-8 |ref| + 1e-4 (fork_ref_util.decode_tol): one launch over prefix rows of 1, 255, 256, 257 and 513 rows
