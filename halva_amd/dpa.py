@@ -439,9 +439,11 @@ class FlatTrainables:
             p.data = self.flat[o:o + n].view_as(p)
             p.main_grad = self.grad[o:o + n].view_as(p)
             p.grad_sink = True
+            p.flat_owner = self          # LoraGroup reads .epoch through it: a write to `flat` moves no tensor version counter
         self.master = self.flat.float()
         self.total = total
         self.post_sync = []          # callbacks run after the bf16 compute copy was refreshed from the fp32 master
+        self.epoch = 0               # number of refreshes of the compute copy (what the parameters' version counters do not see)
 
     def segment(self, pred):
         """Contiguous [lo, hi) covering the parameters whose name satisfies pred (they must be adjacent)."""
@@ -456,6 +458,7 @@ class FlatTrainables:
 
     def sync_compute_copy(self):
         self.flat.copy_(self.master)
+        self.epoch += 1              # before the callbacks: a refresh_tail among them records the new epoch
         for fn in self.post_sync:
             fn()
 

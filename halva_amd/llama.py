@@ -80,6 +80,16 @@ K_ = K      # the kernels module under a name that _LoraGroupFn's local `K` (in_
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
 
 
+def _mm_f32(a, b):
+    """a b as fp32: the bf16 product's fp32 accumulator, not rounded on the way out"""
+    return torch.mm(a, b) if a.dtype == torch.float32 else torch.mm(a, b, out_dtype=torch.float32)
+
+
+def _addmm_f32(c, a, b):
+    """c + a b as fp32, c fp32"""
+    return torch.addmm(c, a, b) if a.dtype == torch.float32 else torch.addmm(c, a, b, out_dtype=torch.float32)
+
+
 class _LoraGroupFn(torch.autograd.Function):
     """y = [residual +] x W^T + scale * concat_g( (x A_g^T) B_g^T )  for G LoRA targets sharing one fused base weight -
     peft 0.4.0 Linear.forward (result += lora_B(lora_A(dropout(x))) * scaling; dropout forced to 0 by the reference,
@@ -143,7 +153,17 @@ class _LoraGroupFn(torch.autograd.Function):
             r = A.shape[0] // len(Bs)
             # [rows, K + G r] = [dx through W | scale * dy_g B_g].  With the transposed copy the product runs in hipBLASLt's
             # NT form (both operands K-major), measured 12 % faster than NN at these shapes on MI355X.
-            dxa = torch.mm(dy2, WcT.t()) if WcT is not None else torch.mm(dy2, Wc)
+            if merged:                                      # (WcT's base rows hold (W + scale B A)^T, LoraGroup.refresh_tail: dx is complete)
+                dxa = torch.mm(dy2, WcT.t())
+            else:
+                # unmerged (A/B forms): the LoRA columns first, then dx = dy W + da A with BOTH products accumulated in fp32 and ONE
+                # rounding to bf16.  (Until the per-element check of tests/test_lora_group_elementwise_gpu.py this was bf16(dy W) with
+                # da A added onto it in place: where dy W fell next to a bf16 midpoint the stored intermediate could take the other
+                # neighbour, a whole ulp of it, and the second rounding carried that into dx.)
+                dxa = torch.empty(dy2.shape[0], xa2.shape[1], dtype=dy2.dtype, device=dy2.device)
+                torch.mm(dy2, WcT[K:].t() if WcT is not None else Wc[:, K:], out=dxa[:, K:])
+                W = WcT[:K].t() if WcT is not None else Wc[:, :K]
+                dxa[:, :K].copy_(_addmm_f32(_mm_f32(dxa[:, K:K + A.shape[0]], A), dy2, W))
             da = dxa[:, K:K + A.shape[0]]
             # Weight gradients of the factors: one side of each product is only r..G r wide and the contraction runs over every token
             # row, a shape the library serves with 32-86 tiles.  With an f32 sink they go through the split-k kernel
@@ -168,8 +188,6 @@ class _LoraGroupFn(torch.autograd.Function):
             else:
                 gA, *gBs = [torch.mm(L.t(), R) for _, L, R, _ in prods]
                 dA, dBs = gA, [gB * scale for gB in gBs]
-            if not merged:                                  # (merged: WcT's base rows already hold (W + scale B A)^T, LoraGroup.refresh_tail)
-                dxa[:, :K].addmm_(da, A)                    # + the LoRA path's contribution to dx, in place
         else:
             dxa = torch.zeros(dy2.shape[0], xa2.shape[1], dtype=dy2.dtype, device=dy2.device)
             dxa[:, :K].copy_(torch.mm(dy2, Wc[:, :K]))
@@ -217,8 +235,12 @@ class LoraGroup(nn.Module):
     """A fused frozen weight [sum(out_g), in] plus the LoRA factors of its G targets.
 
     Storage: `weight_cat` is [N, in + G*r]: columns [0, in) hold the frozen base weight (`.weight` is that strided view),
-    the tail holds blockdiag(scale * B_g) - refreshed from the trainable B parameters whenever they changed (their tensor
-    version counter moves on every optimizer step)."""
+    the tail holds blockdiag(scale * B_g).  Three pieces of state are derived from the trainable factors: that tail, its transpose in
+    `weight_cat_t[in:]`, and - with DGRAD_MERGED - the merged rows (W + scale B A)^T in `weight_cat_t[:in]`.  refresh_tail() writes
+    all three; forward calls it when a factor changed since the last refresh.  A change is seen through the factors' tensor version
+    counters (`p.copy_` under no_grad, load_state_dict, an optimizer stepping the parameter itself) and through the epoch of the
+    dpa.FlatTrainables the factors are bound to (AdamWFlat.step, a resume through sync_compute_copy).  A write through `p.data`, or
+    straight into a flat buffer without sync_compute_copy, moves neither and stays invisible: call refresh_tail() by hand after it."""
 
     def __init__(self, names, in_features, outs, dtype, device):
         super().__init__()
@@ -302,7 +324,13 @@ class LoraGroup(nn.Module):
                 # W^T into `out` with the framework's element-wise copy first - 0.45 ms per group, 30 ms per step over the model)
                 K_.transpose_into(self.weight_cat_t[:K], self.weight_cat[:, :K])
                 self.weight_cat_t[:K].addmm_(self.A_cat.data.t(), self.weight_cat_t[K:K + G * r])
-        self._tail_versions = tuple(B._version for B in self._Bs()) + (self.A_cat._version,)
+        self._tail_versions = self._factor_versions()
+
+    def _factor_versions(self):
+        """What refresh_tail records and forward compares: the factors' tensor version counters, and the epoch of the flat buffer
+        (dpa.FlatTrainables) each factor is bound to, -1 for none - a refresh of that buffer moves no version counter."""
+        ps = self._Bs() + [self.A_cat]
+        return tuple(p._version for p in ps) + tuple(getattr(getattr(p, "flat_owner", None), "epoch", -1) for p in ps)
 
     def merge_(self):
         """peft's merge_and_unload for this group, for inference and export: each target's rows of the base weight become
@@ -348,7 +376,7 @@ class LoraGroup(nn.Module):
             raise ValueError("LoraGroup expects an operand buffer of width %d, got %d" % (self.in_width, xa.shape[-1]))
         if self.A_cat is not None and use_lora:
             Bs = self._Bs()
-            if self._tail_versions != tuple(B._version for B in Bs) + (self.A_cat._version,):
+            if self._tail_versions != self._factor_versions():
                 self.refresh_tail()
             return _LoraGroupFn.apply(xa, residual, self.weight_cat, self.weight_cat_t, self.A_cat, self.scale, self.grad_sink,
                                       self.in_features, res_inplace, self.dgrad_merged, *Bs)

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 import gemm_ref_util as R  # noqa: E402
 from halva_amd import dpa, llama  # noqa: E402
+from lora_group_ref_util import wgrad_operands  # noqa: E402
 from test_gemm_elementwise_gpu import wgrad_slabs  # noqa: E402
 
 DEV = "cuda"
@@ -62,12 +63,8 @@ def test_lora_group_weight_gradient_routes_agree(r, monkeypatch):
         assert R.same_bits(d, dxa) and R.same_bits(x, xa), "%s: the weight-gradient route changed dxa" % name
 
     # (left, right, factor) of every product, in the order of the parameters: the A factors' rows, then each B
-    Gr = 3 * r
-    prods = [(dxa[:, K_IN:K_IN + Gr], xa[:, :K_IN], 1.0)]
-    off = 0
-    for i, n in enumerate(OUTS):
-        prods.append((dy[:, off:off + n], xa[:, K_IN + i * r:K_IN + (i + 1) * r], scale))
-        off += n
+    prods = wgrad_operands(dy, xa, dxa, K_IN, OUTS, r, scale)
+    assert len(prods) == 4 and prods[0][0].shape == (ROWS, 3 * r) and [p[2] for p in prods] == [1.0, scale, scale, scale]
     for q, (L, Rt, f) in enumerate(prods):
         ref = f * (L.double().t() @ Rt.double())
         S = f * (L.double().abs().t() @ Rt.double().abs())
